@@ -7,7 +7,13 @@ temporal re-interpolation -> argmax per pass, SIMPLE label fusion per frame. Wit
 is N videos; the global clip list is sharded clip-wise across ranks and each rank fuses the videos
 whose clips it holds (one video per GPU: no exchange -- weak scaling).
 
-Also reported on the same line (rank 0):
+A plain run (no --full) sets up, warms up, times the steps and prints the line: only the headline
+figures (value, ms_per_step) and the workload's description are filled, the objects below are null.
+--dump-outputs DIR also writes what the last timed step returned (the fused masks of every video this
+rank fused, or the config[3] seg / motion tensors) as DIR/<name>.npy (float32; inputs and weights are
+seeded, so two builds can be compared output for output).
+
+With --full, also reported on the same line (rank 0):
   roofline      the dominant kernel: MFMA work it issues (Winograd-domain products, padded
                 channels) / its mean launch time, HIP events on the launch stream, vs the fp32 peak;
                 algorithmic_equiv_tflops credits the direct-convolution MACs it replaces instead
@@ -22,7 +28,8 @@ Also reported on the same line (rank 0):
                 (pinned H2D overlapped with compute, device preprocessing, async D2H of the masks):
                 the PCIe-inclusive rate, never the headline value
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via torch.distributed.run.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; for N > 1 via
+torch.distributed.run.
 """
 import argparse
 import json
@@ -47,6 +54,7 @@ NORTHSTAR = {"echo": os.path.join(REPO, "tests", "golden", "northstar_c1.npz"),
              "deep": os.path.join(REPO, "tests", "golden", "northstar_c1_deep.npz")}
 BENCH_WEIGHTS = "echo"           # seeded weights whose masks follow the synthetic LV (weights.echo_state_dict)
 DICE_BAR = {"fp32": 1e-3, "bf16": 1e-2}  # north_star: Dice within 1e-3 (fp32), 1e-2 (bf16/fp16)
+DUMP_BUDGET = 48 * 2**20         # bytes --dump-outputs may write in all (every rank, every array)
 
 
 def parse(argv=None):
@@ -57,6 +65,14 @@ def parse(argv=None):
                          "must equal --gpus")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the per-kernel timing pass (roofline, "
+                         "forward, kernels), the parity checks against the CPU fixtures, the CPU baseline and the "
+                         "bf16 / config3 / c2_ragged / stream / fuse_extra runs, each still subject to its own "
+                         "switch below; without --full none of them runs and their objects are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the arrays the last timed step returned as DIR/<name>.npy "
+                         "(float32; a seeded sample of the elements where they exceed the size budget)")
     ap.add_argument("--videos-per-gpu", type=int, default=1)
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--fuse", type=int, default=None, help="shifted passes per video (c1: 5, c2: 1)")
@@ -94,6 +110,8 @@ def parse(argv=None):
                     help="c2: also time the same batch with this many shifted passes (0: off); reported as 'fuse_extra'")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launched ranks (0: free)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.fuse is None:
         args.fuse = 1 if args.workload == "c2" else 5
     return args
@@ -134,13 +152,46 @@ def host_cpus():
     return max(1, n)
 
 
-def timed(fn, steps, warmup, engine, world, dev, kt_fn=None):
+class OutputDump:
+    """--dump-outputs: host copies of what the last timed step of the headline run returned, taken
+    right after the timed region and written as DIR/<name>.npy (float32). The budget DUMP_BUDGET is
+    split evenly over the ranks and this rank's arrays; a larger array is stored as a fixed seeded
+    sample of its elements (flat indices rng(0).integers(0, size, n), sorted)."""
+
+    def __init__(self, path, world):
+        self.path, self.world, self.arrays = path, world, {}
+
+    def snapshot(self, named):
+        if self.path:
+            for name, t in named.items():
+                self.arrays[name] = t.detach().to(torch.float32).cpu().numpy()
+
+    def write(self):
+        if not self.path:
+            return
+        os.makedirs(self.path, exist_ok=True)
+        budget = DUMP_BUDGET // self.world // max(len(self.arrays), 1)
+        for name, a in self.arrays.items():
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.nbytes > budget:
+                idx = np.sort(np.random.default_rng(0).integers(0, a.size, budget // a.itemsize))
+                a = a.reshape(-1)[idx]
+            np.save(os.path.join(self.path, name + ".npy"), a)
+
+
+def mask_names(out):
+    return {f"fused_masks_video{v:04d}": t for v, t in out.items()}
+
+
+def timed(fn, steps, warmup, engine, world, dev, kt_fn=None, kernel_timing=True, keep=None):
     """Run fn warmup times, then time exactly `steps` calls bracketed by barrier + synchronize (the
-    throughput pass, no per-launch events). Then a kernel-timing pass: `steps` more calls of kt_fn
+    throughput pass, no per-launch events); keep(last result) is called right after it. Then, with
+    kernel_timing, a kernel-timing pass: `steps` more calls of kt_fn
     (default fn) with the engine's per-kernel HIP events on. kt_fn is the one-stream form of a step
     whose throughput pass keeps several steps in flight on different streams: there an event interval
     would also hold the other streams' kernels, so per-launch durations come from the serial pass.
-    Returns (max-over-ranks seconds of the throughput pass, kernel timing, last result)."""
+    Returns (max-over-ranks seconds of the throughput pass, kernel timing ({} without the pass), last
+    result)."""
     out = None
     for _ in range(warmup):
         out = fn()
@@ -158,6 +209,10 @@ def timed(fn, steps, warmup, engine, world, dev, kt_fn=None):
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    if keep is not None:
+        keep(out)
+    if not kernel_timing:
+        return float(t.item()), {}, out
     engine.set_kernel_timing(True)
     for _ in range(steps):
         (kt_fn or fn)()
@@ -212,6 +267,8 @@ def kernel_table(kt, engine_dtype):
     """Per kernel class: launches, summed ms, the work it issues on ITS matrix pipe (f32 or bf16) as a
     rate and a fraction of that pipe's peak, the algorithmic (direct-convolution) rate, and the PMC
     MFMA-busy fraction from the committed clock / busy summary."""
+    if not kt:  # no kernel-timing pass (plain run)
+        return None
     busy, src = pmc_mfma_busy(engine_dtype)
     out = {}
     for k, v in kt.items():
@@ -234,6 +291,8 @@ def kernel_table(kt, engine_dtype):
 
 
 def forward_stats(kt, clips, gflop_per_clip, peak, engine_dtype="fp32"):
+    if not kt:  # no kernel-timing pass (plain run)
+        return None
     ms = sum(v["ms"] for v in kt.values())
     alg = gflop_per_clip * clips / (ms * 1e-3) / 1e3 if ms > 0 else 0.0
     # time the matrix pipes would need at their peaks for the work issued, over the summed kernel time
@@ -422,14 +481,16 @@ def main():
     from clasfv_amd.model import R2plus1D_18_MotionNet
     model = R2plus1D_18_MotionNet(pretrained=False, dtype=args.dtype, device=dev, weights=BENCH_WEIGHTS)
     run = {"c1": run_c1, "c2": run_c2, "c3": run_c3_only}[args.workload]
-    line = run(args, model, world, rank, dev)
+    dump = OutputDump(args.dump_outputs, world)
+    line = run(args, model, world, rank, dev, dump)
+    dump.write()
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
 
-def c3_run(args, model, world, dev, steps, warmup):
+def c3_run(args, model, world, dev, steps, warmup, dump=None):
     import clasfv_amd.synthetic as S
     from clasfv_amd.preprocess import zeroone_normalize_
     eng = model.engine
@@ -446,7 +507,9 @@ def c3_run(args, model, world, dev, steps, warmup):
             return model(x)
 
     torch.cuda.synchronize()
-    dt, kt, _ = timed(fwd, steps, warmup, eng, world, dev, kt_fn=lambda: model(x))
+    suffix = f"_rank{dist.get_rank()}" if world > 1 else ""
+    dt, kt, _ = timed(fwd, steps, warmup, eng, world, dev, kt_fn=lambda: model(x), kernel_timing=args.full,
+                      keep=dump and (lambda o: dump.snapshot({"seg" + suffix: o[0], "motion" + suffix: o[1]})))
     n = args.c3_batch * steps * world
     peak = BF16_PEAK_TFLOPS if eng.dtype == "bf16" else FP32_PEAK_TFLOPS
     return {"value": round(n / dt, 3), "unit": "64x224x224 clips/s", "ms_per_step": round(dt / steps * 1e3, 3),
@@ -457,12 +520,12 @@ def c3_run(args, model, world, dev, steps, warmup):
                     "forward signature; the CLI path is fixed at 112x112 (src/fuse_utils.py:22)"}
 
 
-def run_c3_only(args, model, world, rank, dev):
-    res = c3_run(args, model, world, dev, args.steps, args.warmup)
+def run_c3_only(args, model, world, rank, dev, dump):
+    res = c3_run(args, model, world, dev, args.steps, args.warmup, dump)
     return {"metric": "64f×224×224 clips/sec (BASELINE config[3])", "value": res["value"], "unit": res["unit"],
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": model.engine.dtype,
-            "data": "synthetic", "config": {"workload": "BASELINE config[3]: 64-frame 224x224 clips, model forward",
+            "full": args.full, "data": "synthetic", "config": {"workload": "BASELINE config[3]: 64-frame 224x224 clips, model forward",
                                             "batch": args.c3_batch},
             "roofline": res["roofline"], "forward": res["forward"]}
 
@@ -486,7 +549,7 @@ def c2_lengths(args):
     return [args.frames] * args.c2_videos
 
 
-def c2_measure(args, model, world, rank, dev, lengths, fuse, steps, warmup):
+def c2_measure(args, model, world, rank, dev, lengths, fuse, steps, warmup, dump=None):
     """One config[2]-style run: the batch of videos `lengths` sharded clip-wise over the ranks, fused on
     each video's owner; the owner all_to_all (dist.exchange_to_owners) is timed with events on the
     compute stream around the margin computation and the collective (max over ranks)."""
@@ -519,24 +582,25 @@ def c2_measure(args, model, world, rank, dev, lengths, fuse, steps, warmup):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    dt, kt, out = timed(step, steps, 0, eng, world, dev, kt_fn=lambda: serial_step(evs))
+    dt, kt, out = timed(step, steps, 0, eng, world, dev, kt_fn=lambda: serial_step(evs), kernel_timing=args.full,
+                        keep=dump and (lambda o: dump.snapshot(mask_names(o))))
     ex_ms = sum(a.elapsed_time(b) for a, b in evs) / steps if evs else 0.0
     t = torch.tensor([ex_ms], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     fwd = forward_stats(kt, (hi - lo) * steps, GFLOP_PER_CLIP, peak, args.dtype)
     rows, nbytes = D.exchange_stats(lengths, fuse, args.step, world)
-    xfer_ms = exchange_transfer_ms(lengths, fuse, args.step, rank, world, dev) if rows else 0.0
+    xfer_ms = exchange_transfer_ms(lengths, fuse, args.step, rank, world, dev) if rows and args.full else 0.0
     mine = {"rank": rank, "clips": hi - lo, "videos_held": len(needed), "videos_fused": len(out),
-            "forward_ms_per_step": round(sum(v["ms"] for v in kt.values()) / steps, 3)}
+            "forward_ms_per_step": round(sum(v["ms"] for v in kt.values()) / steps, 3) if args.full else None}
     per_rank = gather_ranks(mine, world)
     del videos
     torch.cuda.empty_cache()
     return {"value": round(n_total * steps / dt, 3), "unit": "clips/s", "ms_per_step": round(dt / steps * 1e3, 3),
             "clips_per_step": n_total, "fuse": fuse, "steps_in_flight": inflight, "forward": fwd, "per_rank": per_rank,
             "rows_exchanged_per_step": rows, "bytes_exchanged_per_step": nbytes,
-            "exchange_ms_per_step": round(float(t.item()), 4),
-            "exchange_transfer_ms": round(xfer_ms, 4),
+            "exchange_ms_per_step": round(float(t.item()), 4) if args.full else None,
+            "exchange_transfer_ms": round(xfer_ms, 4) if args.full else None,
             "exchange_note": "margin planes (fp32, 32 x 112 x 112 per crossing clip) through one all_to_all_single "
                              "(RCCL over xGMI with nccl; host-staged with gloo). exchange_ms_per_step = events on the "
                              "compute stream around logit_margin + the collective inside the timed steps, max over "
@@ -571,14 +635,14 @@ def exchange_transfer_ms(lengths, fuse, step, rank, world, dev, reps=5):
     return float(t.item())
 
 
-def run_c2(args, model, world, rank, dev):
+def run_c2(args, model, world, rank, dev, dump):
     """BASELINE config[2]: a fixed batch of full videos (64 x 200 frames, or seeded ragged 100-300-frame
     lengths with --c2-lengths ragged) sharded clip-wise over the ranks (strong scaling). f = 1: 384
     clips for the equal batch; the fuse_extra run repeats it with f = 5."""
     lengths = c2_lengths(args)
-    main_run = c2_measure(args, model, world, rank, dev, lengths, args.fuse, args.steps, args.warmup)
+    main_run = c2_measure(args, model, world, rank, dev, lengths, args.fuse, args.steps, args.warmup, dump)
     extra = None
-    if args.c2_extra_fuse and args.c2_extra_fuse != args.fuse:
+    if args.full and args.c2_extra_fuse and args.c2_extra_fuse != args.fuse:
         extra = c2_measure(args, model, world, rank, dev, lengths, args.c2_extra_fuse, max(2, args.steps // 3), 1)
         extra = {k: v for k, v in extra.items() if k not in ("kt", "out")}
     lv = [float(o.float().mean().item()) for o in main_run["out"].values()]
@@ -588,7 +652,7 @@ def run_c2(args, model, world, rank, dev):
     return {
         "metric": METRIC, "value": main_run["value"], "unit": "clips/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": main_run["ms_per_step"], "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype,
+        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "full": args.full,
         "data": "synthetic EchoNet-style videos (seeded), seeded synthetic weights (" + BENCH_WEIGHTS + " recipe)",
         "config": {"workload": f"BASELINE config[2]: batch of {desc}, "
                                f"{args.fuse} shifted pass(es), clips sharded over {world} rank(s) + per-frame "
@@ -607,7 +671,7 @@ def run_c2(args, model, world, rank, dev):
     }
 
 
-def run_c1(args, model, world, rank, dev):
+def run_c1(args, model, world, rank, dev, dump):
     """BASELINE config[1] per GPU (the headline): each rank fuses its own 200-frame video(s) with 5
     shifted passes (weak scaling)."""
     from clasfv_amd import dist as D
@@ -639,18 +703,21 @@ def run_c1(args, model, world, rank, dev):
         with torch.cuda.stream(s):
             return serial_step()
 
-    dt, ktimes, out = timed(step, args.steps, args.warmup, eng, world, dev, kt_fn=serial_step)
+    dt, ktimes, out = timed(step, args.steps, args.warmup, eng, world, dev, kt_fn=serial_step,
+                            kernel_timing=args.full, keep=lambda o: dump.snapshot(mask_names(o)))
     value = n_total * args.steps / dt
     peak = BF16_PEAK_TFLOPS if args.dtype == "bf16" else FP32_PEAK_TFLOPS
     fwd = forward_stats(ktimes, (hi - lo) * args.steps, GFLOP_PER_CLIP, peak, args.dtype)
     lv_frac = float(np.mean([o.float().mean().item() for o in out.values()])) if out else 0.0
-    parity = northstar_parity(args, out[0], args.dtype) if 0 in out else None
-    parity_random = random_recipe_parity(args, model, serial_step, args.dtype) if world == 1 and args.parity_random else None
+    full = args.full  # everything below the headline figures runs only with --full
+    parity = northstar_parity(args, out[0], args.dtype) if full and 0 in out else None
+    parity_random = (random_recipe_parity(args, model, serial_step, args.dtype)
+                     if full and world == 1 and args.parity_random else None)
     parity_deep = (random_recipe_parity(args, model, serial_step, args.dtype, "deep")
-                   if world == 1 and args.parity_random else None)
+                   if full and world == 1 and args.parity_random else None)
 
     bf16 = None
-    if args.extra_bf16 and args.dtype == "fp32":
+    if full and args.extra_bf16 and args.dtype == "fp32":
         ref_masks = {k: v.clone() for k, v in out.items()}
         model.set_compute_dtype("bf16")
         dt16, k16, out16 = timed(step, args.steps, args.warmup, eng, world, dev, kt_fn=serial_step)
@@ -671,12 +738,12 @@ def run_c1(args, model, world, rank, dev):
                         "Dice tolerance 1e-2"}
         model.set_compute_dtype("fp32")
 
-    c3 = c3_run(args, model, world, dev, max(2, args.steps // 2), 1) if args.extra_c3 else None
+    c3 = c3_run(args, model, world, dev, max(2, args.steps // 2), 1) if full and args.extra_c3 else None
 
     # N > 1: the ragged config[2] batch, whose straddling videos move logit margins between ranks (the
     # c1 layout, one equal video per rank, exchanges nothing)
     c2r = None
-    if args.extra_c2_ragged and world > 1:
+    if full and args.extra_c2_ragged and world > 1:
         import clasfv_amd.synthetic as S
         c2r = c2_measure(args, model, world, rank, dev, S.echonet_like_lengths(args.c2_videos), 1,
                          max(2, args.steps // 2), 1)
@@ -685,7 +752,7 @@ def run_c1(args, model, world, rank, dev):
                            f"100-300 frames, f = 1, clips sharded over {world} ranks (strong scaling)")
 
     stream = None
-    if args.extra_stream and world == 1:
+    if full and args.extra_stream and world == 1:
         import clasfv_amd.synthetic as S
         from clasfv_amd.stream import VideoStream
         hv = [S.echo_video_uint8(args.frames, seed=v) for v in range(8)]
@@ -703,7 +770,7 @@ def run_c1(args, model, world, rank, dev):
                           "async D2H of the uint8 masks; PCIe-inclusive, one host sync per batch of videos"}
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if full and rank == 0 and world == 1 and args.cpu_baseline:
         import clasfv_amd.synthetic as S
         cpu = cpu_baseline(args, S)
 
@@ -719,6 +786,7 @@ def run_c1(args, model, world, rank, dev):
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": args.dtype,
+        "full": full,
         "dtype_note": ("fp32 activations, weights and accumulation; the Winograd convs (layer1-3) on f32 "
                        "MFMAs; the stem, strided / 1x1x1 convs, layer4 convs, decoder projections, comb_2 "
                        "and heads on split-bf16 MFMAs (3 bf16 pieces per operand, 6 products, fp32 "
@@ -732,8 +800,8 @@ def run_c1(args, model, world, rank, dev):
                    "steps_in_flight": inflight,
                    "timing": "value / ms_per_step: the throughput pass, consecutive steps round-robin on "
                              "steps_in_flight HIP streams (one engine workspace per stream), no per-launch "
-                             "events; roofline / forward / kernels: a second pass of the same steps on one "
-                             "stream with the engine's per-launch HIP events",
+                             "events; roofline / forward / kernels (--full): a second pass of the same steps on "
+                             "one stream with the engine's per-launch HIP events",
                    "parallelism": f"clip-shard x{world}; videos fused on the rank holding their clips "
                                   f"(owner all_to_all of logit margins only for straddling videos)"},
         "roofline": kernel_roofline(ktimes, peak, args.dtype),

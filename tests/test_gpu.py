@@ -1424,15 +1424,15 @@ def test_config2_ragged_over_8_ranks_exchanges_and_equals_one_rank(echo_model):
 
 @pytest.mark.timeout(400)
 def test_bench_c1_line_parity_with_steps_in_flight():
-    """The default bench line at N = 1 keeps two steps in flight, and every parity object it reports --
+    """The --full bench line at N = 1 keeps two steps in flight, and every parity object it reports --
     fp32 and bf16, against the echo / random / deep CPU fixtures -- is within its bar (the recipe
     checks run one-stream steps after a device sync: a step in flight on the other stream once
     handed its masks to the host before they were written)."""
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--extra-c3", "0", "--extra-stream", "0",
-           "--cpu-baseline", "0"]
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--extra-c3", "0",
+           "--extra-stream", "0", "--cpu-baseline", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=380, cwd=REPO, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1447,6 +1447,32 @@ def test_bench_c1_line_parity_with_steps_in_flight():
     assert line["parity_deep_weights"]["ed_es_pairs_equal"] and line["parity_deep_weights"]["ef_delta_max_per_systole"] <= 1e-3
 
 
+@pytest.mark.timeout(200)
+def test_bench_plain_run_is_lean_and_dumps_last_step_masks(tmp_path):
+    """A plain bench run (no --full) fills only the headline figures -- every extra object is null --
+    and --dump-outputs writes the last timed step's fused masks as float32 .npy: the config[1] video's
+    masks, within the north_star bar of the CPU reference path's (tests/golden/northstar_c1.npz)."""
+    import json
+    import subprocess
+    import sys
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=REPO, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "clips/s" and line["dtype"] == "fp32"
+    assert abs(line["value"] - 30 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]  # 30 clips per step
+    for k in ("roofline", "forward", "kernels", "cpu_baseline", "parity", "parity_random_weights", "parity_deep_weights",
+              "bf16", "config3", "c2_ragged", "stream"):
+        assert line[k] is None, k
+    assert sorted(os.listdir(tmp_path / "d")) == ["fused_masks_video0000.npy"]
+    got = np.load(tmp_path / "d" / "fused_masks_video0000.npy")
+    ref = unpack_labels(golden("northstar_c1.npz"), "fused_simple")
+    assert got.dtype == np.float32 and got.shape == ref.shape == (200, 112, 112)
+    assert set(np.unique(got)) <= {0.0, 1.0} and dice_delta(got.astype(np.int64), ref) <= DICE_TOL
+
+
 @pytest.mark.timeout(400)
 @pytest.mark.parametrize("workload", ["c1", "c2", "c2r"])
 def test_bench_self_launches_ranks(workload):
@@ -1456,7 +1482,7 @@ def test_bench_self_launches_ranks(workload):
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
            "--extra-bf16", "0", "--extra-c3", "0", "--extra-stream", "0", "--cpu-baseline", "0",
            "--workload", workload[:2]]
     if workload == "c2":

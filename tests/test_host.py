@@ -345,6 +345,38 @@ def test_bench_rejects_world_size_mismatch():
     assert r.returncode != 0 and "must agree" in r.stderr
 
 
+def test_bench_output_dump_budget_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays within the budget are written whole as float32; a larger one is
+    written as the same seeded sample of its elements on every run, and the files stay within the
+    budget."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET <= 64 * 10**6
+    assert bench.parse(["--steps", "7"]).full is False and bench.parse(["--full"]).full is True
+    assert bench.parse([]).dump_outputs is None
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096)
+    small = torch.arange(6, dtype=torch.uint8).view(2, 3)
+    big = torch.arange(5000, dtype=torch.float32).view(50, 100) * 0.5
+    for run in ("a", "b"):
+        d = bench.OutputDump(str(tmp_path / run), world=1)
+        d.snapshot(bench.mask_names({3: small}))
+        d.snapshot({"seg": big})
+        d.write()
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    b = {f: np.load(tmp_path / "b" / f) for f in sorted(os.listdir(tmp_path / "b"))}
+    assert list(a) == list(b) == ["fused_masks_video0003.npy", "seg.npy"]
+    np.testing.assert_array_equal(a["fused_masks_video0003.npy"], small.numpy().astype(np.float32))
+    assert a["seg.npy"].dtype == np.float32 and a["seg.npy"].shape == (512,)  # 4096 B / 2 arrays / 4 B
+    np.testing.assert_array_equal(a["seg.npy"], b["seg.npy"])
+    assert np.isin(a["seg.npy"], big.numpy()).all() and len(np.unique(a["seg.npy"])) > 256
+    off = bench.OutputDump(None, world=1)
+    off.snapshot({"seg": big})
+    off.write()
+    assert off.arrays == {}
+
+
 def test_itk_voting_oracle_rule():
     from oracle import fuse_ref
     a = np.array([[0, 1], [1, 1]], np.uint8)

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/bf16buf}; mkdir -p $out; export TMPDIR=/tmp
 timeout -k 10 400 python -u -m pytest tests/test_gpu.py -x -v --timeout 120 --timeout-method thread -k "buffer_dmas or store_cache" > $out/pytest.log 2>&1 || { echo "tests failed"; tail -30 $out/pytest.log; exit 1; }
 tail -2 $out/pytest.log
-B="bench.py --dtype bf16 --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
+B="bench.py --full --dtype bf16 --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
 for rep in 1 2 3; do
 for v in buf ptr; do
   unset CLASFV_NO_DMA_BUF

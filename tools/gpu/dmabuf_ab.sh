@@ -11,7 +11,7 @@ done
 cat $out/cb.txt
 for v in 0 1 0 1; do
   if [ $v = 1 ]; then export CLASFV_NO_DMA_BUF=1; else unset CLASFV_NO_DMA_BUF; fi
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0 > $out/bench_$v.json 2> $out/bench_$v.err || { echo "bench failed"; tail -20 $out/bench_$v.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0 > $out/bench_$v.json 2> $out/bench_$v.err || { echo "bench failed"; tail -20 $out/bench_$v.err; exit 1; }
   python -c "
 import json; d=json.loads(open('$out/bench_$v.json').read().strip().splitlines()[-1]); k=d['kernels']['kernels']
 print('no_dma_buf=$v', d['value'], d['ms_per_step'], 'dma_x3 ms/fwd', round(k['conv_dma_x3']['ms']/10*k['conv_dma_x3']['launches']/k['conv_dma_x3']['launches'],4), 'proj', round(k['conv_proj_x3']['ms'],3))

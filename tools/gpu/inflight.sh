@@ -2,7 +2,7 @@
 # bench c1 with 1, 2, 3 steps in flight on round-robin streams (A B A), fp32 + bf16 lines, no extras
 out=${1:-gpurun_out/inflight}; mkdir -p $out; export TMPDIR=/tmp
 for k in 1 2 3 1 2; do
-  timeout -k 10 300 python -u bench.py --inflight $k --steps 20 --extra-c3 0 --extra-stream 0 --cpu-baseline 0 --parity-random 0 > $out/bench_$k.log 2>&1 || { echo "bench $k failed"; tail -30 $out/bench_$k.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --inflight $k --steps 20 --extra-c3 0 --extra-stream 0 --cpu-baseline 0 --parity-random 0 > $out/bench_$k.log 2>&1 || { echo "bench $k failed"; tail -30 $out/bench_$k.log; exit 1; }
   python3 - $out/bench_$k.log $k <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -6,7 +6,7 @@ for rep in 1 2; do
 for v in base dma; do
   unset CLASFV_W4R_CACHED_STORES CLASFV_WINOT_NT_STORES CLASFV_DMA_NT_STORES
   [ $v = dma ] && export CLASFV_DMA_NT_STORES=1
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0 > $out/bench_$v.json 2> $out/bench_$v.err || { echo "bench failed"; tail -20 $out/bench_$v.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0 > $out/bench_$v.json 2> $out/bench_$v.err || { echo "bench failed"; tail -20 $out/bench_$v.err; exit 1; }
   python -c "
 import json; d=json.loads(open('$out/bench_$v.json').read().strip().splitlines()[-1]); k=d['kernels']['kernels']
 print('$v', d['value'], d['ms_per_step'], 'wino4r', round(k['conv_wino4r']['ms']/20,4), 'winot', round(k['conv_winot']['ms']/20,4), 'dma_x3', round(k['conv_dma_x3']['ms']/20,4), 'parity', d['parity']['dice_delta_fused_masks'])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # non-temporal output stores, forward A/B: conv_dma_x3 (fp32 bench) and conv_patch32_bf16 (bf16 bench)
 out=${1:-gpurun_out/ntab3}; mkdir -p $out; export TMPDIR=/tmp
-B="bench.py --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
+B="bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
 for rep in 1 2; do
 for v in base dma bf16base bf16patch; do
   unset CLASFV_DMA_NT_STORES CLASFV_PATCH_NT_STORES

@@ -1,7 +1,7 @@
 #!/bin/bash
 # bf16 forward A/B: conv_patch_bf16 non-temporal output stores, conv_patch32_bf16 cached stores
 out=${1:-gpurun_out/ntab4}; mkdir -p $out; export TMPDIR=/tmp
-B="bench.py --dtype bf16 --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
+B="bench.py --full --dtype bf16 --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
 for rep in 1 2 3; do
 for v in base patchnt p32cached; do
   unset CLASFV_PATCH_NT_STORES CLASFV_PATCH32_CACHED_STORES

@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/parity_fix}; mkdir -p $out; export TMPDIR=/tmp
 timeout -k 10 450 python -u -m pytest tests/test_gpu.py -x -v --timeout 400 --timeout-method thread -k "bench_c1_line_parity or concurrent_streams" > $out/pytest.log 2>&1 || { echo "tests failed"; tail -40 $out/pytest.log; exit 1; }
 tail -3 $out/pytest.log
-timeout -k 10 400 python -u bench.py > $out/bench.log 2>&1 || { echo "bench failed"; tail -30 $out/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $out/bench.log 2>&1 || { echo "bench failed"; tail -30 $out/bench.log; exit 1; }
 python3 - $out/bench.log <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

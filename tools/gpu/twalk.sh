@@ -14,7 +14,7 @@ cat $out/cb.txt
 unset CB_NORES CB_CHECK
 timeout -k 10 600 python -u -m pytest tests/test_gpu.py -x -v --timeout 300 --timeout-method thread -k "bf16 or config4" > $out/pytest.log 2>&1 || { echo "tests failed"; tail -60 $out/pytest.log | cut -c1-400; exit 1; }
 tail -2 $out/pytest.log
-timeout -k 10 300 python -u bench.py --extra-c3 0 --extra-stream 0 --cpu-baseline 0 > $out/bench.log 2>&1 || { echo "bench failed"; tail -30 $out/bench.log; exit 1; }
+timeout -k 10 300 python -u bench.py --full --extra-c3 0 --extra-stream 0 --cpu-baseline 0 > $out/bench.log 2>&1 || { echo "bench failed"; tail -30 $out/bench.log; exit 1; }
 python3 - $out/bench.log <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/x3_wr}; mkdir -p $out; export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest tests/test_gpu.py -x -v --timeout 120 --timeout-method thread -k "dma_w or buffer_dmas or x3 or proj or golden" > $out/pytest.log 2>&1 || { echo "tests failed"; tail -30 $out/pytest.log; exit 1; }
 tail -2 $out/pytest.log
-B="bench.py --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
+B="bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --parity-random 0 --extra-bf16 0 --extra-c3 0 --extra-stream 0 --extra-c2-ragged 0"
 for rep in 1 2 3; do
 for v in wr nowr; do
   unset CLASFV_NO_DMA_W
