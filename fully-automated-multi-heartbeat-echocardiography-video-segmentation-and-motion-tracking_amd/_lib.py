@@ -31,6 +31,13 @@ SIGNATURES = {
     "clasfv_kernel_timing": (c_int, [_P, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int),
                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_double)]),
+    "clasfv_conv_count": (c_int, [_P]),
+    "clasfv_conv_info": (c_int, [_P, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_char_p), ctypes.POINTER(c_int),
+                                 ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                 ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "clasfv_run_conv": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, c_int64,
+                                ctypes.POINTER(c_char_p), _P]),
+    "clasfv_run_decoder": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "clasfv_build_clips": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P]),
     "clasfv_pass_labels": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "clasfv_pass_labels_margin": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

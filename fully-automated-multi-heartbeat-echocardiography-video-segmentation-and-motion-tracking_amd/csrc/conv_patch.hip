@@ -249,16 +249,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC))) void
   // epilogue: acc[i][j] holds channels n0 + 16j + 4q .. +3 of block voxel 16*(MT*wid + i) + l16
   const __bf16* res = reinterpret_cast<const __bf16*>(p.res);
   __bf16* y = reinterpret_cast<__bf16*>(p.y);
-  // global voxel index of block voxel m (false outside the map)
+  // global voxel index of block voxel m (false outside the map; gm is then a voxel inside it: the staged
+  // epilogue loads the residual of every block voxel, and a frame past To of the last clip lies past
+  // the tensor)
   auto voxel = [&](int m, size_t& gm) __attribute__((always_inline)) {
-    const int f = m >> 6, px = m & 63, to = t0 + f;
+    const int f = m >> 6, px = m & 63, to = t0 + f, tc = to < p.To ? to : 0;
     if constexpr (G::SPATIAL) {
       const int ho = h0 + (px >> 3), wo = w0 + (px & 7);
-      gm = (((size_t)clip * p.To + to) * p.Ho + (ho < p.Ho ? ho : 0)) * p.Wo + (wo < p.Wo ? wo : 0);
+      gm = (((size_t)clip * p.To + tc) * p.Ho + (ho < p.Ho ? ho : 0)) * p.Wo + (wo < p.Wo ? wo : 0);
       return to < p.To && ho < p.Ho && wo < p.Wo;
     } else {
       const int hw = hw0 + px;
-      gm = ((size_t)clip * p.To + to) * HW + (hw < HW ? hw : 0);
+      gm = ((size_t)clip * p.To + tc) * HW + (hw < HW ? hw : 0);
       return to < p.To && hw < HW;
     }
   };

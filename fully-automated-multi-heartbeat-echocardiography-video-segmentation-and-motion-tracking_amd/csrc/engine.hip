@@ -645,6 +645,50 @@ struct DeviceGuard {
   if (_guard.err != hipSuccess)                                                                 \
     return fail(CLASFV_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(_guard.err))
 
+// The forward context of launch stream s with an arena of at least `bytes`: created on first use; past
+// kMaxCtx streams the least recently used one is taken over once the device is idle (no queued work
+// can still be using its arena).
+int acquire_ctx(clasfv_engine* h, hipStream_t s, size_t bytes, clasfv_engine::Ctx** out) {
+  clasfv_engine::Ctx* cx = nullptr;
+  for (auto* c : h->ctxs)
+    if (c->stream == s) cx = c;
+  if (!cx) {
+    constexpr size_t kMaxCtx = 4;
+    if (h->ctxs.size() < kMaxCtx) {
+      cx = new clasfv_engine::Ctx();
+      h->ctxs.push_back(cx);
+    } else {
+      HIP_TRY(hipDeviceSynchronize());
+      cx = h->ctxs.front();
+      for (auto* c : h->ctxs)
+        if (c->last_use < cx->last_use) cx = c;
+    }
+    cx->stream = s;
+  }
+  cx->last_use = ++h->ctx_clock;
+  if (bytes > cx->arena_bytes) {
+    // The arena may still be in use by work queued earlier on its stream.
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(cx->arena);
+    cx->arena = nullptr;
+    cx->arena_bytes = 0;
+    HIP_TRY(hipMalloc(&cx->arena, bytes));
+    cx->arena_bytes = bytes;
+  }
+  *out = cx;
+  return CLASFV_OK;
+}
+
+// Conv i of the diagnostics' numbering: the backbone convs in execution order, then the decoder
+// projections proj[0], proj[2], proj[3], proj[4] (tap index in *tap; -1 for a backbone conv).
+const Conv* probe_conv(const clasfv_engine* h, int i, int* tap) {
+  static const int kTap[4] = {0, 2, 3, 4};
+  const int nb = (int)h->convs.size();
+  if (i < 0 || i >= nb + 4) return nullptr;
+  if (tap) *tap = i < nb ? -1 : kTap[i - nb];
+  return i < nb ? &h->convs[i] : &h->proj[kTap[i - nb]];
+}
+
 }  // namespace
 
 extern "C" {
@@ -951,34 +995,8 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   DEVICE_GUARD(h->device);
   Layout L;
   make_layout(N, T, H, W, L);
-  // this stream's context: created on first use; past kMaxCtx streams the least recently used one is
-  // taken over once the device is idle (no queued work can still be using its arena)
-  clasfv_engine::Ctx* cx = nullptr;
-  for (auto* c : h->ctxs)
-    if (c->stream == s) cx = c;
-  if (!cx) {
-    constexpr size_t kMaxCtx = 4;
-    if (h->ctxs.size() < kMaxCtx) {
-      cx = new clasfv_engine::Ctx();
-      h->ctxs.push_back(cx);
-    } else {
-      HIP_TRY(hipDeviceSynchronize());
-      cx = h->ctxs.front();
-      for (auto* c : h->ctxs)
-        if (c->last_use < cx->last_use) cx = c;
-    }
-    cx->stream = s;
-  }
-  cx->last_use = ++h->ctx_clock;
-  if (L.total > cx->arena_bytes) {
-    // The arena may still be in use by work queued earlier on its stream.
-    HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(cx->arena);
-    cx->arena = nullptr;
-    cx->arena_bytes = 0;
-    HIP_TRY(hipMalloc(&cx->arena, L.total));
-    cx->arena_bytes = L.total;
-  }
+  clasfv_engine::Ctx* cx = nullptr;  // this stream's context
+  if (int rc_ = acquire_ctx(h, s, L.total, &cx)) return rc_;
   char* const arena = cx->arena;
   auto buf = [&](int b) { return reinterpret_cast<void*>(arena + L.off[b]); };
   int last_ev = h->ktime ? tick(h, s) : -1;
@@ -1167,6 +1185,98 @@ int clasfv_kernel_timing(clasfv_t h, int cap, const char** names, int* launches,
   h->recs.clear();
   h->nev = 0;
   return n;
+}
+
+// ---- diagnostics: one conv / the decoder alone, through the forward's own dispatch ---------------
+
+int clasfv_conv_count(clasfv_t h) { return h ? (int)h->convs.size() + 4 : CLASFV_EINVAL; }
+
+int clasfv_conv_info(clasfv_t h, int i, const char** prefix, const char** bn_prefix, int* tap, int channels[5],
+                     int kernel[3], int stride[3], int padding[3], int* in_dtype, int* out_dtype) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  int tp = -1;
+  const Conv* pc = probe_conv(h, i, &tp);
+  if (!pc) return fail(CLASFV_EINVAL, "bad conv index");
+  Conv c = *pc;  // padded widths and dtypes of the handle's current compute dtype
+  layout_conv(c, h->dtype == CLASFV_DTYPE_BF16);
+  if (prefix) *prefix = pc->w.c_str();
+  if (bn_prefix) *bn_prefix = pc->bn.c_str();
+  if (tap) *tap = tp;
+  if (channels) channels[0] = c.cin, channels[1] = c.cout, channels[2] = c.cin_p, channels[3] = c.cout_p, channels[4] = c.cin2;
+  if (kernel) kernel[0] = c.kt, kernel[1] = c.kh, kernel[2] = c.kw;
+  if (stride) stride[0] = c.st, stride[1] = c.sh, stride[2] = c.sw;
+  if (padding) padding[0] = c.pt, padding[1] = c.ph, padding[2] = c.pw;
+  if (in_dtype) *in_dtype = c.in_bf16 ? CLASFV_DTYPE_BF16 : CLASFV_DTYPE_FP32;
+  if (out_dtype) *out_dtype = c.out_bf16 ? CLASFV_DTYPE_BF16 : CLASFV_DTYPE_FP32;
+  return CLASFV_OK;
+}
+
+int clasfv_run_conv(clasfv_t h, int i, const void* x, int N, int T, int H, int W, const void* x2, const void* res,
+                    int relu, int x_c8, int y_c8, void* y, void* scratch, int64_t scratch_bytes,
+                    const char** kernel_name, void* stream) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  if (!h->ready) return fail(CLASFV_ENOTREADY, "clasfv_finalize has not been called");
+  const Conv* c = probe_conv(h, i, nullptr);
+  if (!c) return fail(CLASFV_EINVAL, "bad conv index");
+  if (!x || !y) return fail(CLASFV_EINVAL, "null tensor");
+  if (N < 1 || T < 1 || H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad shape");
+  if ((c->cin2 != 0) != (x2 != nullptr)) return fail(CLASFV_EINVAL, "second input: needed by the dual projection only");
+  if (scratch_bytes < 0 || (scratch_bytes > 0 && !scratch)) return fail(CLASFV_EINVAL, "bad scratch");
+  if (T + 2 * c->pt < c->kt || H + 2 * c->ph < c->kh || W + 2 * c->pw < c->kw)
+    return fail(CLASFV_EINVAL, "input smaller than the kernel");
+  DEVICE_GUARD(h->device);
+  const Shape5 in{N, T, H, W, c->cin_p};
+  Shape5 out;
+  const char* kname = "";
+  int rc = run_conv(*c, x, in, y, out, res, relu != 0, (hipStream_t)stream, h->zero, x2, &kname, h->tune, x_c8, y_c8,
+                    scratch_bytes ? scratch : nullptr, (size_t)scratch_bytes);
+  if (kernel_name) *kernel_name = kname;
+  return rc;
+}
+
+int clasfv_run_decoder(clasfv_t h, const float* p01, const float* p2, const float* p3, const float* p4, int N, int T,
+                       int H, int W, float* seg, float* mot, void* stream) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  if (!h->ready) return fail(CLASFV_ENOTREADY, "clasfv_finalize has not been called");
+  if (!p01 || !p2 || !p3 || !p4 || !seg || !mot) return fail(CLASFV_EINVAL, "null tensor");
+  if (N < 1 || T < 1 || H < 2 || W < 2) return fail(CLASFV_EINVAL, "bad shape");
+  if (H % 8 || W % 16) return fail(CLASFV_EBADSHAPE, "decoder tiles: H % 8 == 0 and W % 16 == 0");
+  hipStream_t s = (hipStream_t)stream;
+  DEVICE_GUARD(h->device);
+  // the index table lives where the forward keeps it: in this stream's arena, sized and laid out for a
+  // whole forward of this shape (a later clasfv_forward of the shape reuses the arena as it stands)
+  Layout L;
+  make_layout(N, T, H, W, L);
+  clasfv_engine::Ctx* cx = nullptr;
+  if (int rc = acquire_ctx(h, s, L.total, &cx)) return rc;
+  // tap resolutions as the backbone produces them: the stem halves H and W, layer2..4 halve T, H, W
+  // (3-wide kernels, stride 2, padding 1: d -> (d - 1) / 2 + 1)
+  auto half = [](int d) { return (d - 1) / 2 + 1; };
+  const float* taps[4] = {p01, p2, p3, p4};
+  DecParams d{};
+  int t = T, hh = half(H), ww = half(W);
+  for (int k = 0; k < 4; ++k) {
+    if (k) t = half(t), hh = half(hh), ww = half(ww);
+    d.tap[k].p = taps[k];
+    d.tap[k].T = t, d.tap[k].H = hh, d.tap[k].W = ww;
+    d.tap[k].st = tap_scale(t, T);
+    d.tap[k].sh = tap_scale(hh, H);
+    d.tap[k].sw = tap_scale(ww, W);
+  }
+  d.b1 = h->b1;
+  d.w2 = h->w2;
+  d.b2 = h->b2;
+  d.wh = h->wh;
+  d.bh = h->bh;
+  d.seg = seg;
+  d.mot = mot;
+  d.N = N, d.T = T, d.H = H, d.W = W;
+  d.bf16 = h->dtype == CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_BF16);
+  d.w2x3 = h->w2x3;
+  d.x3 = h->dtype != CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_X3);
+  d.idx = cx->arena + L.off[DIDX];
+  HIP_TRY(launch_decoder(d, s));
+  return CLASFV_OK;
 }
 
 int clasfv_build_clips(const float* video, int T, int H, int W, const int32_t* table, int n, int interp, float* clips,

@@ -90,6 +90,40 @@ class Engine:
         _lib.check(self.lib.clasfv_forward(self.h, _lib.ptr(x), n, t, hh, ww, _lib.ptr(seg), _lib.ptr(mot),
                                            _lib.stream_ptr(stream, self.device)), "clasfv_forward")
 
+    # ---- diagnostics: one layer alone (tests) ---------------------------------------------------------
+    def conv_table(self):
+        """One dict per conv of clasfv_conv_info (backbone in execution order, then P01, P2, P3, P4)."""
+        out = []
+        pre, bn = ctypes.c_char_p(), ctypes.c_char_p()
+        tap, din, dout = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        ch, k, s, p = (ctypes.c_int * 5)(), (ctypes.c_int * 3)(), (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+        for i in range(self.lib.clasfv_conv_count(self.h)):
+            _lib.check(self.lib.clasfv_conv_info(self.h, i, ctypes.byref(pre), ctypes.byref(bn), ctypes.byref(tap), ch, k, s,
+                                                 p, ctypes.byref(din), ctypes.byref(dout)), "clasfv_conv_info")
+            out.append({"index": i, "prefix": pre.value.decode(), "bn": bn.value.decode(), "tap": tap.value,
+                        "cin": ch[0], "cout": ch[1], "cin_p": ch[2], "cout_p": ch[3], "cin2": ch[4],
+                        "kernel": tuple(k), "stride": tuple(s), "padding": tuple(p),
+                        "in_dtype": torch.bfloat16 if din.value == 1 else torch.float32,
+                        "out_dtype": torch.bfloat16 if dout.value == 1 else torch.float32})
+        return out
+
+    def run_conv(self, i, x, nthw, y, x2=None, res=None, relu=True, x_c8=False, y_c8=False, scratch=None, stream=None):
+        """clasfv_run_conv on device tensors in the engine's layouts; returns the kernel's name."""
+        name = ctypes.c_char_p()
+        n, t, hh, ww = nthw
+        opt = lambda a: _lib.ptr(a) if a is not None else None
+        _lib.check(self.lib.clasfv_run_conv(self.h, i, _lib.ptr(x), n, t, hh, ww, opt(x2), opt(res), int(bool(relu)),
+                                            int(bool(x_c8)), int(bool(y_c8)), _lib.ptr(y), opt(scratch),
+                                            scratch.numel() * scratch.element_size() if scratch is not None else 0,
+                                            ctypes.byref(name), _lib.stream_ptr(stream, self.device)), "clasfv_run_conv")
+        return name.value.decode()
+
+    def run_decoder(self, taps, nthw, seg, mot, stream=None):
+        """clasfv_run_decoder over the four projected taps (channels-last fp32, 64 channels)."""
+        n, t, hh, ww = nthw
+        _lib.check(self.lib.clasfv_run_decoder(self.h, *[_lib.ptr(a) for a in taps], n, t, hh, ww, _lib.ptr(seg),
+                                               _lib.ptr(mot), _lib.stream_ptr(stream, self.device)), "clasfv_run_decoder")
+
     def set_kernel_timing(self, enable=True):
         """Per-kernel HIP-event timing of every later forward (see clasfv_kernel_timing)."""
         _lib.check(self.lib.clasfv_set_kernel_timing(self.h, 1 if enable else 0), "clasfv_set_kernel_timing")

@@ -144,6 +144,35 @@ int clasfv_set_kernel_timing(clasfv_t h, int enable);
 int clasfv_kernel_timing(clasfv_t h, int cap, const char** names, int* launches, double* ms,
                          double* gflop, double* xgflop);
 
+/* ---- diagnostics: one layer alone (for layer-level tests; not on the reference's interface) - */
+/* New exports only: the ABI revision is unchanged. Convs are numbered in execution order: the
+ * backbone's (stem.0, stem.3, layer1.0.conv1.0.0, ...), then the decoder's tap projections P01 (dual
+ * input: stem tap and layer1 tap), P2, P3, P4. */
+int clasfv_conv_count(clasfv_t h);
+/* Conv i for the handle's current compute dtype. prefix / bn_prefix: state-dict prefixes of the conv
+ * weight and its BatchNorm ("" for a projection, whose weights are columns of comb_1_layer: *tap is
+ * its tap 0, 2, 3 or 4, and -1 for a backbone conv). channels = {cin, cout, cin_p, cout_p, cin2}
+ * (cin_p, cout_p: padded widths of the engine's tensors; cin2: width of the second input, P01 only);
+ * kernel, stride, padding as (t, h, w); in / out dtype CLASFV_DTYPE_*. Any output pointer may be NULL. */
+int clasfv_conv_info(clasfv_t h, int i, const char** prefix, const char** bn_prefix, int* tap, int channels[5],
+                     int kernel[3], int stride[3], int padding[3], int* in_dtype, int* out_dtype);
+/* Run conv i alone, exactly as clasfv_forward would (same kernel choice, variants, weight images and
+ * split-K rule), on caller-owned device tensors in the engine's layouts: x (N,T,H,W,cin_p)
+ * channels-last, or 8-channel-blocked [cin_p/8][N*T*H*W][8] when x_c8; y and res (may be NULL, may
+ * alias y) the same over the conv's output voxels and cout_p; x2 the second input of P01 (NULL
+ * otherwise); dtypes as clasfv_conv_info reports. scratch: split-K partial sums (4 * M * cout_p
+ * floats enable it; NULL / 0: never split). *kernel_name: the kernel that ran (static string).
+ * CLASFV_EINVAL for a layout the chosen kernel does not take. */
+int clasfv_run_conv(clasfv_t h, int i, const void* x_dev, int N, int T, int H, int W, const void* x2_dev,
+                    const void* res_dev, int relu, int x_c8, int y_c8, void* y_dev, void* scratch_dev,
+                    int64_t scratch_bytes, const char** kernel_name, void* stream);
+/* Run the decoder alone over caller-supplied 64-channel projected taps (channels-last fp32) with the
+ * handle's head weights: p01 at (T, H', W'), H' = (H - 1) / 2 + 1, and p2, p3, p4 each halving T, H'
+ * and W' again the same way (d -> (d - 1) / 2 + 1). H % 8 == 0 and W % 16 == 0 (CLASFV_EBADSHAPE). */
+int clasfv_run_decoder(clasfv_t h, const float* p01_dev, const float* p2_dev, const float* p3_dev,
+                       const float* p4_dev, int N, int T, int H, int W, float* seg_dev, float* motion_dev,
+                       void* stream);
+
 /* ---- clip plumbing: replaces src/fuse_utils.py:16-100 ----------------------------------------- */
 /* Build n clips (n,3,32,H,W) from the normalised video (3,T,H,W). Clip i is frames
  * [table[2i+1], table[2i+1]+32) of the temporally shifted video video[:, table[2i]:], resampled
