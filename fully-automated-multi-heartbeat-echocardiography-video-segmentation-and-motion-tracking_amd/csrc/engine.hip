@@ -1287,18 +1287,38 @@ int clasfv_build_clips(const float* video, int T, int H, int W, const int32_t* t
   return CLASFV_OK;
 }
 
+// Shared argument check of clasfv_pass_labels[_margin]. Beyond the pointers: every pass must have the
+// clips its frames are read from (what fuse_utils.clip_table raises for), and T is a grid dimension.
+static int check_pass_labels(const void* in, int K, const int32_t* clip0, int T, int step, int H, int W, int interp,
+                             const void* labels) {
+  if (!in || !clip0 || !labels || K < 1 || K > CLASFV_MAX_PASSES || T < 1 || step < 1)
+    return fail(CLASFV_EINVAL, "bad argument (K must be in [1, 64])");
+  if (H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad argument (H and W must be >= 1)");
+  if (T > 65535) return fail(CLASFV_EINVAL, "bad argument (T must be <= 65535)");
+  if ((int64_t)(K - 1) * step >= T) return fail(CLASFV_EINVAL, "bad argument ((K - 1) * step must be < T)");
+  for (int k = 0; k < K; ++k) {
+    const int tk = T - k * step;
+    const int q = tk >> 5, r = tk & 31;
+    const int nk = r > 16 ? q + 1 : r < 16 ? q : q + (q & 1);  // round half to even, as build_clips
+    if (nk == 0) return fail(CLASFV_EINVAL, "a pass has too few frames for one 32-frame clip");
+    if (clip0[k] < 0) return fail(CLASFV_EINVAL, "negative pass_clip0 entry");
+    // Without resampling frame f of the pass is frame f of its clips: 32 * nk > tk would need a clip that
+    // cannot be built (clip_table's ValueError), 32 * nk < tk leaves frames [32 * nk, tk) without logits.
+    if (!interp && r != 0) return fail(CLASFV_EINVAL, "interpolate == 0 needs every pass length to be a multiple of 32");
+  }
+  return CLASFV_OK;
+}
+
 int clasfv_pass_labels(const float* logits, int K, const int32_t* clip0, int T, int step, int H, int W, int interp,
                        uint8_t* labels, void* stream) {
-  if (!logits || !clip0 || !labels || K < 1 || K > CLASFV_MAX_PASSES || T < 1 || step < 1)
-    return fail(CLASFV_EINVAL, "bad argument (K must be in [1, 64])");
+  if (int rc = check_pass_labels(logits, K, clip0, T, step, H, W, interp, labels)) return rc;
   HIP_TRY(launch_pass_labels(logits, K, clip0, T, step, H * W, interp, 0, labels, (hipStream_t)stream));
   return CLASFV_OK;
 }
 
 int clasfv_pass_labels_margin(const float* margin, int K, const int32_t* clip0, int T, int step, int H, int W,
                               int interp, uint8_t* labels, void* stream) {
-  if (!margin || !clip0 || !labels || K < 1 || K > CLASFV_MAX_PASSES || T < 1 || step < 1)
-    return fail(CLASFV_EINVAL, "bad argument (K must be in [1, 64])");
+  if (int rc = check_pass_labels(margin, K, clip0, T, step, H, W, interp, labels)) return rc;
   HIP_TRY(launch_pass_labels(margin, K, clip0, T, step, H * W, interp, 1, labels, (hipStream_t)stream));
   return CLASFV_OK;
 }
@@ -1317,6 +1337,11 @@ int clasfv_fuse_votes(const uint8_t* labels, int K, int T, int step, int H, int 
   const int m = method & ~CLASFV_FUSE_FORCE_GENERIC;
   if (m != CLASFV_FUSE_MAJORITY && m != CLASFV_FUSE_SIMPLE && m != CLASFV_FUSE_STAPLE && m != CLASFV_FUSE_ITKVOTING)
     return fail(CLASFV_EINVAL, "unknown method");
+  if (H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad argument (H and W must be >= 1)");
+  if ((m == CLASFV_FUSE_MAJORITY || m == CLASFV_FUSE_ITKVOTING) && T - (step - 1) > 65535)
+    return fail(CLASFV_EINVAL, "bad argument (majority / ITK voting take at most 65535 output frames)");
+  if (m == CLASFV_FUSE_SIMPLE && (int64_t)H * W > CLASFV_SIMPLE_MAX_HW)
+    return fail(CLASFV_EBADSHAPE, "SIMPLE keeps one frame's estimate in LDS: H * W must be <= 162816");
   HIP_TRY(launch_fuse_votes(labels, K, T, step, H * W, method, fused, (hipStream_t)stream));
   return CLASFV_OK;
 }

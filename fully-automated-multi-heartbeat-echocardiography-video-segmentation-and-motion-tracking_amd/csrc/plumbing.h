@@ -4,6 +4,9 @@
 #include <stdint.h>
 
 #define CLASFV_MAX_PASSES 64
+// SIMPLE fusion keeps one frame's estimate (H * W bytes, generic kernel) in dynamic LDS beside at most
+// 1 KB of static arrays: the largest frame that fits the device's 160 KB.
+#define CLASFV_SIMPLE_MAX_HW (160 * 1024 - 1024)
 
 hipError_t launch_build_clips(const float* video, int T, int HW, const int32_t* table, int n, int interp, float* clips,
                               hipStream_t s);

@@ -171,16 +171,26 @@ __global__ void pass_labels_kernel(const float* __restrict__ logits, PassTable t
   }
 }
 
-// (n,2,32,HW) logits -> (n,32,HW) margins d = l1 - l0, 4 voxels per thread.
+// (n,2,32,HW) logits -> (n,32,HW) margins d = l1 - l0, 4 voxels per thread (per_clip is a multiple of 4,
+// so a 16-B vector never straddles clips); one voxel per thread when a pointer is not 16-B aligned.
 __global__ void logit_margin_kernel(const float* __restrict__ logits, int n, size_t per_clip,
                                     float* __restrict__ margin) {
-  const size_t total4 = (size_t)n * per_clip / 4;
-  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total4; g += (size_t)gridDim.x * blockDim.x) {
-    const size_t e = 4 * g, c = e / per_clip, r = e - c * per_clip;
+  if ((((uintptr_t)logits | (uintptr_t)margin) & 15) == 0) {
+    const size_t total4 = (size_t)n * per_clip / 4;
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total4; g += (size_t)gridDim.x * blockDim.x) {
+      const size_t e = 4 * g, c = e / per_clip, r = e - c * per_clip;
+      const float* l = logits + 2 * c * per_clip + r;
+      const f32x4 l0 = *reinterpret_cast<const f32x4*>(l);
+      const f32x4 l1 = *reinterpret_cast<const f32x4*>(l + per_clip);
+      *reinterpret_cast<f32x4*>(margin + e) = l1 - l0;
+    }
+    return;
+  }
+  const size_t total = (size_t)n * per_clip;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = e / per_clip, r = e - c * per_clip;
     const float* l = logits + 2 * c * per_clip + r;
-    const f32x4 l0 = *reinterpret_cast<const f32x4*>(l);
-    const f32x4 l1 = *reinterpret_cast<const f32x4*>(l + per_clip);
-    *reinterpret_cast<f32x4*>(margin + e) = l1 - l0;
+    margin[e] = l[per_clip] - l[0];
   }
 }
 
@@ -794,10 +804,12 @@ hipError_t launch_fuse_votes(const uint8_t* labels, int K, int T, int step, int 
   if (method == 2) {
     hipLaunchKernelGGL(fuse_staple_kernel, dim3(tout), dim3(STAPLE_THREADS), 0, s, labels, K, T, step, HW, fused);
   } else if (method == 1) {
+    // Both kernels keep per-pixel state in dynamic LDS beside static arrays (fast: 2244 B, generic: 544 B).
+    // The default limit is 64 KB for the sum; above it the attribute is raised, up to the 160 KB of a CU.
     const size_t lds = 3 * (size_t)HW;
-    if (K <= SIMPLE_FAST_MAXV && lds <= 160 * 1024 && !force_generic) {
+    if (K <= SIMPLE_FAST_MAXV && lds + 4096 <= 160 * 1024 && !force_generic) {
       static size_t attr = 0;
-      if (lds > 64 * 1024 && lds > attr) {
+      if (lds + 4096 > 64 * 1024 && lds > attr) {
         hipError_t e = hipFuncSetAttribute((const void*)fuse_simple_fast_kernel,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -806,6 +818,14 @@ hipError_t launch_fuse_votes(const uint8_t* labels, int K, int T, int step, int 
       hipLaunchKernelGGL(fuse_simple_fast_kernel, dim3(tout), dim3(SIMPLE_FAST_THREADS), lds, s, labels, K, T, step, HW,
                          fused);
     } else {
+      if (HW > CLASFV_SIMPLE_MAX_HW) return hipErrorInvalidValue;  // clasfv_fuse_votes refuses it first
+      static size_t attr_generic = 0;
+      if ((size_t)HW + 1024 > 64 * 1024 && (size_t)HW > attr_generic) {
+        hipError_t e = hipFuncSetAttribute((const void*)fuse_simple_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           HW);
+        if (e != hipSuccess) return e;
+        attr_generic = HW;
+      }
       hipLaunchKernelGGL(fuse_simple_kernel, dim3(tout), dim3(SIMPLE_THREADS), HW, s, labels, K, T, step, HW, fused);
     }
   } else {

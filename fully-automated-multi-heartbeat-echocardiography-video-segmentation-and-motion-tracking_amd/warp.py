@@ -32,6 +32,9 @@ def _warp_forward(img, motion, out=None):
     n, c, h, w = img.shape
     if out is None:
         out = torch.empty_like(img)
+    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.shape != img.shape or out.device != img.device
+          or not out.is_contiguous()):
+        raise ValueError(f"out= must be a contiguous float32 tensor of img's shape {tuple(img.shape)} on {img.device}")
     lib = _lib.load()
     _lib.check(lib.clasfv_warp(_lib.ptr(img), n, c, h, w, _lib.ptr(motion), motion.stride(0), motion.stride(1),
                                _lib.ptr(out), _lib.stream_ptr(device=img.device)), "clasfv_warp")
@@ -68,7 +71,8 @@ class _Warp(torch.autograd.Function):
 def warp(img, motion, out=None):
     """img (N,C,H,W) float32 on the device, motion (N,2,H,W) (any strides on N and the channel
     dim; H,W contiguous) -> warped (N,C,H,W) = grid_sample(img, generate_2dmotion_field(img, motion),
-    bilinear, border, align_corners=False). Differentiable in img and motion."""
+    bilinear, border, align_corners=False). Differentiable in img and motion. ``out`` (no autograd): a
+    contiguous float32 tensor of img's shape on img's device to write into, else ValueError."""
     if torch.is_grad_enabled() and (img.requires_grad or motion.requires_grad):
         if out is not None:
             raise ValueError("out= is not supported under autograd")

@@ -34,7 +34,7 @@ extern "C" {
 enum {
   CLASFV_OK = 0,
   CLASFV_EINVAL = -1,     /* bad argument / unknown parameter name */
-  CLASFV_EBADSHAPE = -2,  /* shape not supported: T % 8, H % 16, W % 16 must be 0 */
+  CLASFV_EBADSHAPE = -2,  /* shape not supported: T % 8, H % 16, W % 16 must be 0 (forward); frame too large (SIMPLE) */
   CLASFV_ENOTREADY = -3,  /* forward before clasfv_finalize / missing parameters */
   CLASFV_EHIP = -4,       /* HIP runtime error (message in clasfv_last_error) */
   CLASFV_ENOMEM = -5
@@ -183,7 +183,11 @@ int clasfv_build_clips(const float* video_dev, int T, int H, int W, const int32_
 /* For each shifted pass k < K: softmax over the 2 classes of the pass's clips' logits
  * (logits_dev + pass_clip0[k] clips, each (2,32,H,W)), resample to T_k = T - k*step frames
  * (align_corners=False) when T_k % 32 != 0 and interpolate != 0, argmax -> labels_dev[k][0..T_k)
- * (labels_dev is (K,T,H,W) uint8). pass_clip0 is a host array of K ints. */
+ * (labels_dev is (K,T,H,W) uint8; frames [T_k, T) of row k are not written). pass_clip0 is a host array
+ * of K ints. CLASFV_EINVAL, before anything is launched, for H < 1 or W < 1, T > 65535,
+ * (K - 1) * step >= T, a pass whose T_k rounds to no clip (round(T_k / 32) == 0, half to even), and, with
+ * interpolate == 0, a pass with T_k % 32 != 0 (its frames would be read from clips that
+ * clasfv_build_clips cannot build, or have no logits at all). */
 int clasfv_pass_labels(const float* logits_dev, int K, const int32_t* pass_clip0, int T, int step, int H,
                        int W, int interpolate, uint8_t* labels_dev, void* stream);
 /* Same labels from logit margins d = l1 - l0 ((n,32,H,W) per clip, clasfv_logit_margin) instead of
@@ -191,13 +195,16 @@ int clasfv_pass_labels(const float* logits_dev, int K, const int32_t* pass_clip0
  * through fl(l1 - l0). Used for the multi-GPU exchange (half the bytes on xGMI). */
 int clasfv_pass_labels_margin(const float* margin_dev, int K, const int32_t* pass_clip0, int T, int step,
                               int H, int W, int interpolate, uint8_t* labels_dev, void* stream);
-/* margin_dev (n,32,H,W) = logits_dev[:,1] - logits_dev[:,0] for n clips of (2,32,H,W) logits. */
+/* margin_dev (n,32,H,W) = logits_dev[:,1] - logits_dev[:,0] for n clips of (2,32,H,W) logits. Pointers
+ * need float alignment only (16-byte-aligned ones take the vector path). */
 int clasfv_logit_margin(const float* logits_dev, int n, int H, int W, float* margin_dev, void* stream);
 /* Per-frame label fusion over the K <= 64 shifted passes (fuse_utils.py:82-100). Output (T',H,W)
  * uint8 with T' = T - (step - 1). method: CLASFV_FUSE_MAJORITY, CLASFV_FUSE_SIMPLE,
  * CLASFV_FUSE_STAPLE or CLASFV_FUSE_ITKVOTING (LabelFusion's methods, fuse_utils.py:95; SIMPLE,
  * STAPLE and ITK voting are restated from their published definitions: LabelFusion itself is absent,
- * so their parity is unpinned). */
+ * so their parity is unpinned). CLASFV_EINVAL for H < 1 or W < 1 and, for MAJORITY / ITKVOTING, T' > 65535.
+ * SIMPLE keeps one frame's state in LDS: H * W <= 162816 (160 KB less 1 KB; e.g. 403 x 403), else
+ * CLASFV_EBADSHAPE; the packed kernel (K <= 16) serves H * W <= 53248, the generic one everything else. */
 int clasfv_fuse_votes(const uint8_t* labels_dev, int K, int T, int step, int H, int W, int method,
                       uint8_t* fused_dev, void* stream);
 

@@ -118,23 +118,43 @@ def clamp_num_clips(t, num_clips, step):
     return num_clips
 
 
+def labels_from_logits(logits, tk, interpolate_last=True, return_margin=False):
+    """fuse_utils.py:60,66-80 for one pass: (n,2,32,H,W) float32 logits of its n clips -> softmax over
+    the classes -> (2, 32 n, H, W) -> resampled to ``tk`` frames when interpolate_last and tk % 32 != 0 ->
+    argmax. Returns the (tk,H,W) int64 labels of that float32 computation; with ``return_margin`` also the
+    float64 class margin q1 - q0 of the same resampling (float64 softmax of the same logits, p1 - p0 =
+    tanh((l1 - l0) / 2), combined with the same source frames and the same float32 lambdas in float64):
+    where |margin| is far above float32 rounding of a probability, the label is not a matter of rounding."""
+    logits = np.asarray(logits, np.float32)
+    h, w = logits.shape[-2:]
+    if len(logits):
+        p = softmax2(logits).transpose(1, 0, 2, 3, 4).reshape(2, -1, h, w)
+    else:
+        p = np.zeros((2, 0, h, w), np.float32)
+    resample = bool(interpolate_last and tk % 32 != 0)
+    if resample:
+        p = temporal_resample(p, tk, axis=1)
+    labels = (p[1] > p[0]).astype(np.int64)  # np.argmax over 2 classes: ties -> 0
+    if not return_margin:
+        return labels
+    l64 = logits.astype(np.float64)
+    m = np.tanh((l64[:, 1] - l64[:, 0]) / 2.0).reshape(-1, h, w)
+    if resample:
+        i0, i1, l0, l1 = temporal_source_index(m.shape[0], tk)
+        m = m[i0] * l0.astype(np.float64)[:, None, None] + m[i1] * l1.astype(np.float64)[:, None, None]
+    return labels, m
+
+
 def pass_labels(video, model, shift, interpolate_last=True, to_numpy=None):
     """Labels (T-shift, H, W) of one temporally shifted pass (fuse_utils.py:45-80)."""
     clips = divide_to_consecutive_clips(video[:, shift:], interpolate_last=interpolate_last)
-    probs = []
+    segs = []
     for c in clips:
         seg, _ = model(c[None])
         seg = to_numpy(seg) if to_numpy else np.asarray(seg)
-        probs.append(softmax2(seg.astype(np.float32)))
-    h, w = video.shape[2:]
-    if probs:
-        p = np.concatenate(probs).transpose(1, 0, 2, 3, 4).reshape(2, -1, h, w)
-    else:
-        p = np.zeros((2, 0, h, w), np.float32)
-    tk = video.shape[1] - shift
-    if interpolate_last and tk % 32 != 0:
-        p = temporal_resample(p, tk, axis=1)
-    return (p[1] > p[0]).astype(np.int64)  # np.argmax over 2 classes: ties -> 0
+        segs.append(seg.astype(np.float32))
+    logits = np.concatenate(segs) if segs else np.zeros((0, 2, 32) + tuple(video.shape[2:]), np.float32)
+    return labels_from_logits(logits, video.shape[1] - shift, interpolate_last)
 
 
 def majority_vote(votes, class_list=(0, 1)):
@@ -186,7 +206,7 @@ def simple_vote(votes, class_list=(0, 1), t=0.05, stop=25, iterations=25):
     return result
 
 
-def staple_vote(votes, class_list=(0, 1), max_iter=100, tol=1e-7, init=0.99999):
+def staple_vote(votes, class_list=(0, 1), max_iter=100, tol=1e-7, init=0.99999, return_posterior=False):
     """Binary STAPLE (Warfield, Zou & Wells 2004), in the form of ITK's STAPLEImageFilter: rater j's
     decision D_j = (vote == 1); prior f = mean of all decisions; sensitivity p_j / specificity q_j
     start at ``init``; E step W = f*P1 / (f*P1 + (1-f)*P0), P1 = prod_j (p_j if D_j else 1-p_j),
@@ -194,7 +214,9 @@ def staple_vote(votes, class_list=(0, 1), max_iter=100, tol=1e-7, init=0.99999):
     sum W, q_j = sum (1-W)(1-D_j) / sum (1-W) (a zero denominator keeps the old value); stop when no
     p_j, q_j moves by more than ``tol`` or after ``max_iter`` iterations; label 1 where W > 0.5.
     ``fuse_images(..., "staple")`` of LabelFusion (src/fuse_utils.py:95) is absent: PARITY UNPINNED;
-    this is the restatement the GPU kernel (plumbing.hip fuse_staple_kernel) is checked against."""
+    this is the restatement the GPU kernel (plumbing.hip fuse_staple_kernel) is checked against.
+    ``return_posterior``: also the final W (float64, the votes' shape), whose distance from 0.5 says
+    where the label hangs on the last bits of a sum."""
     d = np.stack([np.asarray(v) == 1 for v in votes]).reshape(len(votes), -1)
     nv, npx = d.shape
     f = d.sum() / float(nv * npx)
@@ -221,7 +243,10 @@ def staple_vote(votes, class_list=(0, 1), max_iter=100, tol=1e-7, init=0.99999):
         p, q = np_, nq_
         if done:
             break
-    return (e_step(p, q) > 0.5).astype(np.uint8).reshape(np.asarray(votes[0]).shape)
+    w = e_step(p, q)
+    shape = np.asarray(votes[0]).shape
+    labels = (w > 0.5).astype(np.uint8).reshape(shape)
+    return (labels, w.reshape(shape)) if return_posterior else labels
 
 
 def _weighted_mv(cands, w):
@@ -237,11 +262,22 @@ FUSERS = {"majority": majority_vote, "majorityvoting": majority_vote, "mv": majo
           "itkvoting": itk_voting, "voting": itk_voting, "simple": simple_vote, "staple": staple_vote}
 
 
-def fuse_frames(passes, t, step, fuse_method="simple", class_list=(0, 1)):
-    """Per-frame fusion loop (fuse_utils.py:82-100). ``passes[k]`` is (T-k*step, H, W)."""
+def fuse_frames(passes, t, step, fuse_method="simple", class_list=(0, 1), posterior=None):
+    """Per-frame fusion loop (fuse_utils.py:82-100). ``passes[k]`` is (T-k*step, H, W). ``posterior``
+    (STAPLE only): a list that receives, per fused frame, staple_vote's final W (None for a frame with one
+    vote, which is copied)."""
     if len(passes) == 0:
         raise IndexError("list index out of range")
     fuse = FUSERS[fuse_method.lower()]
+    if posterior is not None:
+        if fuse is not staple_vote:
+            raise ValueError("posterior= is STAPLE's")
+        posterior.append(None)
+
+        def fuse(votes, class_list):
+            labels, w = staple_vote(votes, class_list, return_posterior=True)
+            posterior[-1] = w
+            return labels
     fused = [passes[0][0]]
     for i in range(1, t):
         if step - 1 < i:
@@ -250,6 +286,8 @@ def fuse_frames(passes, t, step, fuse_method="simple", class_list=(0, 1)):
                 if i - idx * step < 0:
                     break
                 votes.append(passes[idx][i - idx * step].astype(np.uint8))
+            if posterior is not None:
+                posterior.append(None)
             if len(votes) <= 1:
                 fused.append(votes[0])
             else:

@@ -241,3 +241,80 @@ def test_deep_fixture_is_physiological_and_depends_on_layer2_4():
             s1, _ = r2plus1d_ref.head(sd, taps[:2] + [t * 0.99 for t in taps[2:]])
         flips[rec] = int(((s0[0, 1] > s0[0, 0]) != (s1[0, 1] > s1[0, 0])).sum())
     assert flips["echo"] == 0 and flips["deep"] > 0, flips
+
+
+def test_labels_from_logits_restates_the_reference_tail():
+    """labels_from_logits (factored out of pass_labels): softmax -> F.interpolate(trilinear,
+    align_corners=False) -> argmax as torch computes them, with the ties, saturated and huge logits the GPU
+    test plants; the float64 margin has the label's sign wherever it is not tiny and is exactly 0 on a tie
+    of both source frames; without resampling it is tanh((l1 - l0) / 2)."""
+    rng = np.random.default_rng(7)
+    h, w = 9, 13
+    logits = rng.normal(0, 2, (2, 2, 32, h, w)).astype(np.float32)
+    logits[:, :, :, 0, 0] = 1.25                       # exact tie in every frame
+    logits[:, 0, :, 0, 1], logits[:, 1, :, 0, 1] = -50, 50    # margin +100: softmax saturates
+    logits[:, 0, :, 0, 2], logits[:, 1, :, 0, 2] = 50, -50
+    logits[:, :, :, 0, 3] = 80
+    logits[:, :, :, 0, 4] = -80
+    for tk in (70, 64, 60):
+        lab, m = fuse_ref.labels_from_logits(logits, tk, True, return_margin=True)
+        p = F.softmax(torch.from_numpy(logits), 1).permute(1, 0, 2, 3, 4).reshape(1, 2, 64, h, w)
+        if tk % 32:
+            p = F.interpolate(p, size=(tk, h, w), mode="trilinear", align_corners=False)
+        ref = np.argmax(p[0].numpy(), 0)
+        assert lab.shape == (tk, h, w) and lab.dtype == np.int64 and m.dtype == np.float64
+        sure = np.abs(m) > 1e-6
+        np.testing.assert_array_equal(lab[sure], ref[sure])
+        np.testing.assert_array_equal(lab[sure], (m > 0)[sure])
+        unsure = ~sure
+        unsure[:, 0, [0, 3, 4]] = False  # the planted ties
+        assert not unsure.any()  # N(0, 2) logits alone leave no margin near 0
+        assert np.all(m[:, 0, 0] == 0) and np.all(lab[:, 0, 0] == 0)
+        assert np.all(m[:, 0, 1] == 1) and np.all(m[:, 0, 2] == -1) and np.all(lab[:, 0, 1] == 1)
+        assert np.all(lab[:, 0, 3:5] == 0) and np.all(m[:, 0, 3:5] == 0)
+        np.testing.assert_array_equal(fuse_ref.labels_from_logits(logits, tk, True), lab)
+    lab, m = fuse_ref.labels_from_logits(logits, 70, False, return_margin=True)  # no resampling: 64 frames
+    assert lab.shape == (64, h, w)
+    d = logits.astype(np.float64)
+    np.testing.assert_array_equal(m, np.tanh((d[:, 1] - d[:, 0]) / 2).reshape(64, h, w))
+    # flipping both signs flips every label that is not a tie
+    flipped, mf = fuse_ref.labels_from_logits(-logits, 70, True, return_margin=True)
+    lab, m = fuse_ref.labels_from_logits(logits, 70, True, return_margin=True)
+    np.testing.assert_array_equal(mf, -m)
+    sure = np.abs(m) > 1e-6
+    np.testing.assert_array_equal(flipped[sure], 1 - lab[sure])
+
+
+def test_staple_posterior_and_fuse_frames_hook():
+    """staple_vote(return_posterior=True): W has the votes' shape, the labels are W > 0.5 and equal the
+    plain call; W is exactly 0 / 1 on unanimous all-background / all-foreground votes and on a 1-vs-1 split
+    of constant images the label is 0. fuse_frames(posterior=[]) hands out the same W per fused frame."""
+    rng = np.random.default_rng(3)
+    truth = (rng.random((12, 10)) > 0.6).astype(np.uint8)
+    votes = []
+    for _ in range(5):
+        v = truth.copy()
+        v[rng.random(truth.shape) < 0.1] ^= 1
+        votes.append(v)
+    lab, w = fuse_ref.staple_vote(votes, return_posterior=True)
+    assert w.shape == truth.shape and w.dtype == np.float64 and lab.dtype == np.uint8
+    np.testing.assert_array_equal(lab, fuse_ref.staple_vote(votes))
+    np.testing.assert_array_equal(lab, w > 0.5)
+    assert np.all((w >= 0) & (w <= 1)) and np.abs(w - 0.5).min() > 1e-9
+    z, o = np.zeros((5, 7), np.uint8), np.ones((5, 7), np.uint8)
+    for k in (2, 3, 64):
+        lab, w = fuse_ref.staple_vote([z] * k, return_posterior=True)
+        assert not lab.any() and np.all(w == 0)
+        lab, w = fuse_ref.staple_vote([o] * k, return_posterior=True)
+        assert lab.all() and np.all(w == 1)
+    assert not fuse_ref.staple_vote([z, o]).any() and not fuse_ref.majority_vote([z, o]).any()
+    assert np.all(fuse_ref.itk_voting([z, o]) == 2)
+    passes = [np.stack([votes[(k + f) % 5] for f in range(6 - k)]) for k in range(3)]
+    post = []
+    fused = fuse_ref.fuse_frames(passes, 6, 1, "staple", posterior=post)
+    np.testing.assert_array_equal(fused, fuse_ref.fuse_frames(passes, 6, 1, "staple"))
+    assert len(post) == len(fused) and post[0] is None and post[1] is None
+    for f in range(2, 6):
+        np.testing.assert_array_equal(fused[f], post[f] > 0.5)
+    with pytest.raises(ValueError):
+        fuse_ref.fuse_frames(passes, 6, 1, "simple", posterior=[])
