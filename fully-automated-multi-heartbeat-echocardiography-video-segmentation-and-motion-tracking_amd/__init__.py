@@ -8,7 +8,8 @@ libclasfv.so). Modules:
 
   model       R2plus1D_18_MotionNet drop-in (forward(x) -> (seg, motion))
   fuse_utils  divide_to_consecutive_clips / segment_a_video_with_fusion drop-ins
-  warp        motion-field warp (generate_2dmotion_field + grid_sample semantics)
+  warp        motion-field warp (generate_2dmotion_field + grid_sample semantics); track /
+              track_labels / apply_sequence_deformation: a frame through a chain of fields
   echo        EF from masks (compute_ef_using_putative_clips, get2dPucks, EDESpairs)
   preprocess  zeroone_normalizer on the device
   dist        clip-wise sharding over ranks + all-gather of per-clip logits

@@ -17,6 +17,7 @@
 #include "clasfv.h"
 #include "common.h"
 #include "plumbing.h"
+#include "track.h"
 
 namespace {
 
@@ -1359,6 +1360,28 @@ int clasfv_warp_backward(const float* grad_out, const float* img, int N, int C, 
     return fail(CLASFV_EINVAL, "bad argument");
   HIP_TRY(launch_warp_backward(grad_out, img, N, C, H, W, motion, m_sn, m_sc, grad_img, grad_motion,
                                (hipStream_t)stream));
+  return CLASFV_OK;
+}
+
+int clasfv_track(const float* img, int N, int C, int H, int W, const float* motion, int64_t m_sn, int64_t m_sc,
+                 int64_t m_st, int T, int t0, int t_step, int P, int mode, float* out, void* stream) {
+  if (!img || !motion || !out) return fail(CLASFV_EINVAL, "bad argument (null pointer)");
+  if (N < 1 || C < 1 || H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad argument (N, C, H and W must be >= 1)");
+  if (P < 1) return fail(CLASFV_EINVAL, "bad argument (P must be >= 1)");
+  if (t_step != 1 && t_step != -1) return fail(CLASFV_EINVAL, "bad argument (t_step must be +1 or -1)");
+  const int64_t t_last = t0 + (int64_t)(P - 1) * t_step;
+  if (T < 1 || t0 < 0 || t0 >= T || t_last < 0 || t_last >= T)
+    return fail(CLASFV_EINVAL, "bad argument (every frame t0 + p * t_step, p < P, must lie in [0, T))");
+  const int both = CLASFV_TRACK_FORCE_STEPS | CLASFV_TRACK_FORCE_LDS, m = mode & ~both;
+  if ((m != CLASFV_TRACK_BILINEAR && m != CLASFV_TRACK_NEAREST) || (mode & both) == both)
+    return fail(CLASFV_EINVAL, "unknown mode");
+  if ((int64_t)H * W > INT32_MAX || (int64_t)N * C > INT32_MAX)
+    return fail(CLASFV_EBADSHAPE, "H * W and N * C must be < 2^31");
+  // step 0 reads img while out[0] is written (out[p - 1] while out[p], which never overlap)
+  const uintptr_t i0 = (uintptr_t)img, o0 = (uintptr_t)out;
+  const uint64_t frame = (uint64_t)N * C * H * W * sizeof(float);
+  if (i0 < o0 + frame * (uint64_t)P && o0 < i0 + frame) return fail(CLASFV_EINVAL, "out overlaps img");
+  HIP_TRY(launch_track(img, N, C, H, W, motion, m_sn, m_sc, m_st, t0, t_step, P, mode, out, (hipStream_t)stream));
   return CLASFV_OK;
 }
 

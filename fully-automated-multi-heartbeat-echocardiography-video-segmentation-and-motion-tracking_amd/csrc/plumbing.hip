@@ -19,6 +19,7 @@
 
 #include "clasfv.h"
 #include "plumbing.h"
+#include "warp_math.h"
 
 // Every fused multiply-add below is written out (fmaf) where PyTorch's CPU kernels contract one;
 // nothing else may be contracted (HIP's __fmul_rn etc. are plain operators defined in a header this pragma does not reach, so
@@ -575,13 +576,7 @@ __global__ __launch_bounds__(STAPLE_THREADS) void fuse_staple_kernel(const uint8
 }
 
 // ---- warp ------------------------------------------------------------------------------------
-// torch.linspace(-1, 1, n) on the CPU: step = 2/(n-1); first half fma(step, i, -1), second half
-// fma(-step, n-1-i, 1) (the kernel is built with FMA contraction).
-__device__ inline float linspace_pm1(int i, int n) {
-  if (n == 1) return -1.f;
-  const float step = 2.0f / (float)(n - 1);
-  return (i < n / 2) ? fmaf(step, (float)i, -1.f) : fmaf(-step, (float)(n - 1 - i), 1.f);
-}
+// linspace_pm1 (torch.linspace(-1, 1, n) on the CPU): warp_math.h, shared with track.hip
 
 // F.grid_sample(bilinear, border, align_corners=False) as PyTorch's vectorised CPU kernel computes it
 // (GridSamplerKernel.cpp, built with FMA contraction; bit-exact vs the reference golden):

@@ -16,8 +16,14 @@ from ``src/loss_functions.py``. The definitions are re-derived from SURVEY.md se
   backward fields to its start; each propagated label is scored with ``seg_criterion`` against the
   softmax of the frame it lands on, except the ED->ES and ES->ED landings, which are scored with a
   Dice loss against the true ES / ED labels (OTS). Returns (flow_loss / (2 (T-2)), ots_loss / 2).
-  The ED- and ES-seeded chains of one direction share their motion fields frame by frame, so they
-  advance together: one stacked warp per frame instead of two.
+  Each of the four chains (ED and ES seeds, forward and backward) is one ``track`` call (one
+  ``clasfv_track`` ABI call). That is one kernel launch per chain only for planes of at most
+  CLASFV_TRACK_LDS_AUTO_PIXELS (48x48) pixels; larger planes, the 112x112 training plane among them,
+  take one launch per step of every chain, and the ED and ES chains of a direction no longer share a
+  stacked launch per frame as they did in the per-frame loop. The backward is one
+  ``clasfv_warp_backward`` per chain step. Measured against that stacked loop (tools/loss_chain_timing.py,
+  DESIGN.md section 8) the loss is 1.15x to 1.2x faster forward + backward (1.3x to 1.4x forward only) at
+  112x112 and 32x40 alike: it is bound by host calls, and ``track`` issues a chain's launches from C.
 * ``DiceLoss`` (src/clasfv_losses.py:11-26), ``huber_loss`` (src/loss_functions.py:66-77),
   ``convert_to_1hot`` (src/loss_functions.py:123-134), ``categorical_dice`` (the numpy metric).
 """
@@ -26,7 +32,7 @@ import torch
 from torch import nn
 
 from .echo import categorical_dice  # noqa: F401  (re-exported: src/clasfv_losses.py:60-68)
-from .warp import warp
+from .warp import track, warp
 
 
 def soft_dice_loss(pred, target, smooth=1.0):
@@ -93,34 +99,23 @@ def deformation_motion_loss(source_videos, motion_field):
     return (0.005 * smooth.sum() + mse.sum()) / 2 / pairs
 
 
-def _propagate(seeds, fields, direction, start, end):
+def _propagate(seeds, motion, direction, start, end):
     """Advance label chains through per-frame displacement fields.
 
-    seeds: {name: (first_frame, one-hot (N,2,H,W))}; a chain seeded at frame f is warped by
-    fields[:, :, f] and lands on f + direction, then by the field of that frame, and so on. As in the
+    seeds: {name: (first_frame, one-hot (N,2,H,W))}; a chain seeded at frame f is warped by the
+    forward (direction +1: channels 0,1) or backward (-1: channels 2,3) field of motion (N,4,T,H,W)
+    at frame f and lands on f + direction, then by the field of that frame, and so on. As in the
     reference's loops, forward chains run while the landing frame is < end (range(seed, end - 1),
     src/clasfv_losses.py:83,97) and backward chains while the warped frame is > start
-    (range(seed, start, -1), :111,125): neither direction looks at the other bound. Chains active
-    at the same frame are stacked into one warp launch. Returns {name: [(landing_frame, warped
-    label), ...]} in propagation order."""
-    n = fields.shape[0]
-    frames = {k: f for k, (f, _) in seeds.items()}
-    state = {k: lab for k, (_, lab) in seeds.items()}
-    out = {k: [] for k in seeds}
-    first = min(frames.values()) if direction > 0 else max(frames.values())
-    f = first
-    while True:
-        land = f + direction
-        if (land >= end) if direction > 0 else (f <= start):
-            break
-        active = [k for k in seeds if (frames[k] <= f if direction > 0 else frames[k] >= f)]
-        if active:
-            stacked = torch.cat([state[k] for k in active])
-            moved = warp(stacked, fields[:, :, f].repeat(len(active), 1, 1, 1))
-            for i, k in enumerate(active):
-                state[k] = moved[i * n:(i + 1) * n]
-                out[k].append((land, state[k]))
-        f = land
+    (range(seed, start, -1), :111,125): neither direction looks at the other bound. Each chain is one
+    ``track`` call (one launch up to 48x48 pixels, else one per step; the chains are not stacked; every
+    step bit-identical to a ``warp`` of the previous frame).
+    Returns {name: [(landing_frame, warped label), ...]} in propagation order."""
+    out = {}
+    for k, (first, lab) in seeds.items():
+        stop = end - 1 if direction > 0 else start
+        moved = track(lab, motion, first, stop, forward=direction > 0)
+        out[k] = [(f + direction, moved[p]) for p, f in enumerate(range(first, stop, direction))]
     return out
 
 
@@ -131,12 +126,10 @@ def motion_seg_loss(label_ed, label_es, ed_index, es_index, motion_output, seg_s
     ed1 = convert_to_1hot(label_ed, 2, dev)
     es1 = convert_to_1hot(label_es, 2, dev)
     ed_index, es_index = int(ed_index), int(es_index)
-    fwd = motion_output[:, 0:2]
-    bwd = motion_output[:, 2:4]
     flow, ots = 0, 0
 
     # forward in time: both chains run until they land on frame end-1
-    chains = _propagate({"ed": (ed_index, ed1), "es": (es_index, es1)}, fwd, +1, start, end)
+    chains = _propagate({"ed": (ed_index, ed1), "es": (es_index, es1)}, motion_output, +1, start, end)
     for land, lab in chains["ed"]:
         if land == es_index:
             ots = ots + soft_dice_loss(lab, es1)
@@ -146,7 +139,7 @@ def motion_seg_loss(label_ed, label_es, ed_index, es_index, motion_output, seg_s
         flow = flow + seg_criterion(seg_softmax[:, :, land], lab)
 
     # backward in time: both chains run until they land on frame start
-    chains = _propagate({"es": (es_index, es1), "ed": (ed_index, ed1)}, bwd, -1, start, end)
+    chains = _propagate({"es": (es_index, es1), "ed": (ed_index, ed1)}, motion_output, -1, start, end)
     for land, lab in chains["es"]:
         if land == ed_index:
             ots = ots + soft_dice_loss(lab, ed1)

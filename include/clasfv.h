@@ -225,6 +225,35 @@ int clasfv_warp_backward(const float* grad_out_dev, const float* img_dev, int N,
                          const float* motion_dev, int64_t m_sn, int64_t m_sc, float* grad_img_dev,
                          float* grad_motion_dev, void* stream);
 
+/* ---- tracking (src/visualization_utils.py:58-130) ------------------------------------------------ */
+/* A chain of clasfv_warp steps that keeps every frame: out (P,N,C,H,W), time-major and dense; frame p is
+ * img (N,C,H,W) after p + 1 warps, through motion frames t0, t0 + t_step, ..., t0 + (P-1) * t_step
+ * (apply_sequence_deformation called with growing end_index; get_deformed_label_forback's series).
+ * motion_dev points at the first channel of the pair to use (the caller offsets to channel 2 for the
+ * backward fields, as for clasfv_warp); element (n,c,t,i,j) is at
+ * motion_dev[n*m_sn + c*m_sc + t*m_st + i*W + j], so a (N,4,T,H,W) tensor is used in place.
+ * mode: CLASFV_TRACK_BILINEAR (each step bit-identical to clasfv_warp) or CLASFV_TRACK_NEAREST
+ * (grid_sample mode="nearest": the clipped source coordinate rounded half to even; for label maps).
+ * Two paths, the same values bit for bit. LDS path: ONE launch, one workgroup per (n, c) plane, the plane
+ * in two LDS buffers of H * W floats (planes of up to CLASFV_TRACK_LDS_MAX_PIXELS fit: 2 * 20480 * 4 B =
+ * the 160 KiB of a CU). Step path: P launches through HBM over the whole chip. By default planes of
+ * H * W <= CLASFV_TRACK_LDS_AUTO_PIXELS take the LDS path (measured faster there: one CU is VALU-bound on
+ * larger planes) and all others the step path; CLASFV_TRACK_FORCE_LDS takes the LDS path for
+ * every plane that fits, CLASFV_TRACK_FORCE_STEPS the step path always (tests, A/B timing).
+ * Stream-ordered; no handle, no workspace. out_dev must not overlap img_dev. CLASFV_EINVAL, before any
+ * HIP call, for a null pointer, P < 1, t_step other than +1 / -1, a used frame outside [0, T), an
+ * unknown mode (both FORCE flags included), N, C, H or W < 1 or out overlapping img; CLASFV_EBADSHAPE for
+ * H * W or N * C >= 2^31. */
+#define CLASFV_TRACK_BILINEAR 0
+#define CLASFV_TRACK_NEAREST 1
+#define CLASFV_TRACK_FORCE_STEPS 0x100 /* OR into mode: take the per-step path (tests, A/B timing) */
+#define CLASFV_TRACK_FORCE_LDS 0x200   /* OR into mode: take the LDS path whenever the plane fits */
+#define CLASFV_TRACK_LDS_MAX_PIXELS 20480
+#define CLASFV_TRACK_LDS_AUTO_PIXELS 2304
+int clasfv_track(const float* img_dev, int N, int C, int H, int W, const float* motion_dev, int64_t m_sn,
+                 int64_t m_sc, int64_t m_st, int T, int t0, int t_step, int P, int mode, float* out_dev,
+                 void* stream);
+
 /* ---- preprocessing (motion_segment.py:96-106, src/echonet_dataset.py:38-50) --------------------- */
 /* frames_dev (T,Hs,Ws,3) uint8 RGB -> out_dev (3,T,H,W) float32, resized as
  * F.interpolate(size=(T,H,W), mode="trilinear", align_corners=True) on the (1,3,T,Hs,Ws) float

@@ -1,0 +1,461 @@
+"""clasfv_track (csrc/track.hip) and its Python surface (warp.track, warp.track_labels,
+apply_sequence_deformation's grid_mode, losses on track), bit for bit against the reference-run golden
+(tests/golden/track.npz) and the CPU oracle (oracle/warp_ref.py).
+
+The kernels are called through the ctypes ABI between guard bands (all-ones bits, which no sample of
+finite data can produce): after a launch the guards are intact and every output element is written.
+Every shape runs on the default dispatch, with CLASFV_TRACK_FORCE_LDS where the plane fits the LDS path, and
+with CLASFV_TRACK_FORCE_STEPS; the paths agree with each other and with the oracle. The oracle keeps only the
+last frame of a chain, so every intermediate frame comes from calling it with a growing end index.
+"""
+import ctypes
+import os
+import re
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import warp_ref
+from tests.conftest import REPO, golden
+from tests.golden.make_golden_losses import loss_inputs
+from tests.golden.make_golden_track import CASES as GOLDEN_CASES, track_inputs
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 4096
+EINVAL, EBADSHAPE = -1, -2
+BILINEAR, NEAREST, FORCE_STEPS, FORCE_LDS = 0, 1, 0x100, 0x200
+MODES = {"bilinear": BILINEAR, "nearest": NEAREST}
+NUL = ctypes.c_void_p(0)
+HEADER = open(os.path.join(REPO, "include", "clasfv.h")).read()
+LDS_MAX_PIXELS = int(re.search(r"#define CLASFV_TRACK_LDS_MAX_PIXELS (\d+)", HEADER).group(1))    # what fits
+LDS_AUTO_PIXELS = int(re.search(r"#define CLASFV_TRACK_LDS_AUTO_PIXELS (\d+)", HEADER).group(1))  # default path
+
+
+def dev():
+    return torch.device("cuda", 0)
+
+
+class Guarded:
+    """numel float32 between two guard bands, sentinel-filled (all-ones bits) throughout."""
+
+    def __init__(self, numel):
+        self.buf = torch.empty(numel + 2 * GUARD, dtype=torch.float32, device=dev())
+        self.raw = self.buf.view(torch.int32)
+        self.raw.fill_(-1)
+        self.lo, self.hi = GUARD, GUARD + numel
+        self.t = self.buf[self.lo:self.hi]
+
+    def guards_intact(self):
+        return bool((self.raw[:self.lo] == -1).all()) and bool((self.raw[self.hi:] == -1).all())
+
+    def all_written(self):
+        return bool((self.raw[self.lo:self.hi] != -1).all())
+
+    def untouched(self):
+        return bool((self.raw == -1).all())
+
+
+def lib():
+    from clasfv_amd import _lib
+    return _lib.load()
+
+
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def call_track(img_p, n, c, h, w, mot, forward, t_len, t0, t_step, count, mode, out_p):
+    """clasfv_track on the current stream, then wait. ``mot``: device (N,4,T,H,W) view (any n, channel and t
+    strides) or a raw pointer with dense strides assumed by the caller. A refusal is returned; a HIP error
+    ends the session: nothing more is launched on a device that has faulted."""
+    from clasfv_amd import _lib
+    if torch.is_tensor(mot):
+        assert mot.stride(4) == 1 or w == 1
+        assert mot.stride(3) == w or h == 1
+        pair = ctypes.c_void_p(mot.data_ptr() + (0 if forward else 2) * mot.stride(1) * 4)
+        sn, sc, st = mot.stride(0), mot.stride(1), mot.stride(2)
+    else:
+        pair, (sn, sc, st) = mot, (4 * t_len * h * w, t_len * h * w, h * w)
+    rc = lib().clasfv_track(img_p, n, c, h, w, pair, sn, sc, st, t_len, t0, t_step, count, mode, out_p,
+                            _lib.stream_ptr(None, dev()))
+    if rc in (EINVAL, EBADSHAPE):
+        return rc
+    if rc != 0:
+        pytest.exit(f"clasfv_track: HIP error ({rc}) {lib().clasfv_last_error()}, stopping the session", returncode=3)
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as ex:
+        pytest.exit(f"clasfv_track: HIP error, stopping the session: {ex}", returncode=3)
+    return rc
+
+
+def run_track(img, mot_d, forward, t0, count, mode):
+    """(P,N,C,H,W) numpy result of one guarded clasfv_track call; img numpy, mot_d a device (N,4,T,H,W) view."""
+    n, c, h, w = img.shape
+    img_d = torch.from_numpy(img).to(dev())
+    out = Guarded(count * img.size)
+    rc = call_track(ptr(img_d), n, c, h, w, mot_d, forward, mot_d.shape[2], t0, 1 if forward else -1, count, mode,
+                    ptr(out.t))
+    assert rc == 0, lib().clasfv_last_error()
+    assert out.guards_intact(), "write outside the tracked frames"
+    assert out.all_written(), "tracked pixels left unwritten"
+    return out.t.cpu().numpy().reshape((count,) + img.shape)
+
+
+def oracle_frames(img, motion, forward, t0, count, mode):
+    """Every frame of the chain from oracle/warp_ref.apply_sequence_deformation with a growing end."""
+    step = 1 if forward else -1
+    ti, tm = torch.from_numpy(img), torch.from_numpy(motion)
+    return np.stack([warp_ref.apply_sequence_deformation(ti, tm, t0, t0 + step * (p + 1), mode, forward).numpy()
+                     for p in range(count)])
+
+
+def paths_for(h, w):
+    """Mode flags of every path a plane of h x w takes: the default dispatch (LDS path up to
+    CLASFV_TRACK_LDS_AUTO_PIXELS, else steps), the forced LDS path (if the plane fits) and the forced step path."""
+    return [("auto", 0)] + ([("lds", FORCE_LDS)] if h * w <= LDS_MAX_PIXELS else []) + [("steps", FORCE_STEPS)]
+
+
+def rng_for(*key):
+    return np.random.default_rng(zlib.crc32(repr(key).encode()))
+
+
+# ---- inputs -------------------------------------------------------------------------------------------
+ZERO_FRAME = 1      # this motion frame is zero flow in every channel
+BEYOND = 1.45       # planted flow past +-1: lands outside the image from its far side too
+
+
+def _source_coordinate(lin, flow, size):
+    """The unclipped source coordinate fma(lin + flow + 1, size / 2, -0.5) in float32, as the kernel and torch
+    compute it (the product of two float32 and the -0.5 are exact in float64: one rounding)."""
+    g1 = ((lin + flow).astype(np.float32) + np.float32(1)).astype(np.float32)
+    return (g1.astype(np.float64) * (size * 0.5) - 0.5).astype(np.float32)
+
+
+def build_motion(rng, n, t, h, w):
+    """(N,4,T,H,W) float32: 1.5 tanh(N(0, 0.4)) (reaches past +-1); on 5 % of the samples a flow aimed at a
+    source coordinate m + 0.5 (exact where 2 (m + 1) / size is a binary fraction); frame ZERO_FRAME all zero;
+    on the other frames +-BEYOND at the first / last pixel (at the only pixel: by the parity of n + t), which
+    lands outside the image at the low / high end of both axes."""
+    m = (1.5 * np.tanh(rng.normal(0, 0.4, (n, 4, t, h, w)))).astype(np.float32)
+    lin = {0: torch.linspace(-1, 1, w).numpy()[None, :], 1: torch.linspace(-1, 1, h).numpy()[:, None]}
+    for ch in range(4):
+        size = (w, h)[ch & 1]
+        floors = rng.integers(0, max(size - 1, 1), (n, t, h, w))
+        aimed = (2.0 * (floors + 1) / size - 1.0 - lin[ch & 1]).astype(np.float32)
+        m[:, ch] = np.where(rng.random((n, t, h, w)) < 0.05, aimed, m[:, ch])
+    m[:, :, ZERO_FRAME] = 0
+    flat = m.reshape(n, 4, t, h * w)
+    for ti in range(t):
+        if ti == ZERO_FRAME:
+            continue
+        if h * w == 1:
+            for ni in range(n):
+                flat[ni, :, ti, 0] = BEYOND if (ni + ti) & 1 else -BEYOND
+        else:
+            flat[:, :, ti, 0] = -BEYOND
+            flat[:, :, ti, -1] = BEYOND
+    return m
+
+
+def check_coverage(motion, forward, frames, h, w, halves):
+    """On the CPU, in float32: the used frames clip at both ends of both axes, and (halves) some source
+    coordinates are exact half-integers with even and with odd floors."""
+    ch = 0 if forward else 2
+    parities = set()
+    for axis, size, lin in ((0, w, torch.linspace(-1, 1, w).numpy()[None, :]),
+                            (1, h, torch.linspace(-1, 1, h).numpy()[:, None])):
+        u = _source_coordinate(lin, motion[:, ch + axis][:, frames], size)
+        assert (u < 0).any() and (u > size - 1).any(), f"axis {axis}: no sample clipped at one end"
+        ix = np.clip(u, np.float32(0), np.float32(size - 1))
+        fl = np.floor(ix)
+        half = (ix - fl) == np.float32(0.5)
+        parities |= set((fl[half].astype(np.int64) & 1).tolist())
+    if halves:
+        assert parities == {0, 1}, f"half-integer source coordinates with floors of parity {parities} only"
+
+
+# (id, N, C, H, W, T, P, t0 forward, t0 backward, halves)
+#   1x1, 1x7, 7x1: one-pixel axes (linspace of one point, every corner outside)    5x9: odd sizes, one wave
+#   112x112 P=31: the workload's plane (13 pixels per thread, the last ragged) through all 32 frames in place
+#   48x48 = CLASFV_TRACK_LDS_AUTO_PIXELS: the last plane on the LDS path by default; 48x49: the first on the step path
+#   128x160 = CLASFV_TRACK_LDS_MAX_PIXELS: the whole 160 KiB, 20 pixels per thread; 128x161: first on the step path
+#   224x224: BASELINE config[3], step path, more than one block per plane
+SHAPES = [("1x1", 3, 2, 1, 1, 4, 3, 0, 3, False), ("1x7", 3, 2, 1, 7, 4, 3, 0, 3, False),
+          ("7x1", 3, 2, 7, 1, 4, 3, 0, 3, False), ("5x9", 3, 2, 5, 9, 4, 3, 0, 3, False),
+          ("5x9-P1", 3, 2, 5, 9, 4, 1, 2, 2, False), ("48x48", 3, 1, 48, 48, 3, 2, 0, 2, True),
+          ("48x49", 3, 1, 48, 49, 3, 2, 0, 2, True), ("112x112", 3, 2, 112, 112, 32, 31, 0, 31, True),
+          ("128x160", 3, 1, 128, 160, 3, 2, 0, 2, True), ("128x161", 3, 1, 128, 161, 3, 2, 0, 2, True),
+          ("224x224", 1, 2, 224, 224, 4, 3, 0, 3, True)]
+
+
+def test_threshold_shapes_straddle_the_header_constant():
+    assert 128 * 160 == LDS_MAX_PIXELS and 128 * 161 > LDS_MAX_PIXELS and 112 * 112 <= LDS_MAX_PIXELS
+    assert 48 * 48 == LDS_AUTO_PIXELS <= LDS_MAX_PIXELS
+    assert 2 * LDS_MAX_PIXELS * 4 <= 160 * 1024
+
+
+@pytest.mark.parametrize("mode", ["bilinear", "nearest"])
+@pytest.mark.parametrize("forward", [True, False], ids=["fwd", "bwd"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: s[0])
+def test_track_vs_oracle(shape, forward, mode):
+    """Every frame of the chain, on every path the shape can take, bit for bit against the oracle (and so the
+    paths against each other). The (N,4,T,H,W) motion tensor is passed in place."""
+    name, n, c, h, w, t, count, t0f, t0b, halves = shape
+    t0 = t0f if forward else t0b
+    step = 1 if forward else -1
+    frames = [t0 + step * p for p in range(count)]
+    rng = rng_for("track", name)
+    img = rng.standard_normal((n, c, h, w)).astype(np.float32)
+    motion = build_motion(rng, n, t, h, w)
+    check_coverage(motion, forward, frames, h, w, halves)
+    ref = oracle_frames(img, motion, forward, t0, count, mode)
+    if ZERO_FRAME in frames and h * w > 1 and mode == "bilinear":
+        # zero flow samples between pixel centres: not the identity (rounded to nearest, it is)
+        p = frames.index(ZERO_FRAME)
+        assert not np.array_equal(ref[p], ref[p - 1] if p else img)
+    mot_d = torch.from_numpy(motion).to(dev())
+    got = {}
+    for path, flag in paths_for(h, w):
+        got[path] = run_track(img, mot_d, forward, t0, count, MODES[mode] | flag)
+        np.testing.assert_array_equal(got[path], ref, err_msg=f"{path} path")
+    if "lds" in got:
+        np.testing.assert_array_equal(got["lds"], got["steps"])
+
+
+@pytest.mark.parametrize("case", GOLDEN_CASES, ids=lambda c: c[0])
+def test_track_vs_reference_golden(case):
+    """The reference's own apply_sequence_deformation (tests/golden/make_golden_track.py), both directions
+    and both grid modes, every intermediate frame, on both paths."""
+    key, forward, start, mode, src = case
+    d = track_inputs()
+    want = golden("track.npz")[key]
+    mot_d = torch.from_numpy(d["motion"]).to(dev())
+    for path, flag in paths_for(*d[src].shape[2:]):
+        got = run_track(d[src], mot_d, forward, start, d["T"], MODES[mode] | flag)
+        np.testing.assert_array_equal(got, want, err_msg=f"{path} path")
+
+
+@pytest.mark.parametrize("mode", ["bilinear", "nearest"])
+@pytest.mark.parametrize("hw", [(5, 9), (24, 20)], ids=["5x9", "24x20"])
+def test_track_motion_strides(hw, mode):
+    """A motion tensor that is a slice of a larger allocation (n, channel and t strides all larger than the
+    dense ones) gives what its dense copy gives."""
+    h, w = hw
+    n, c, t = 3, 2, 5
+    rng = rng_for("strides", hw)
+    img = rng.standard_normal((n, c, h, w)).astype(np.float32)
+    motion = build_motion(rng, n, t, h, w)
+    big = torch.full((n + 1, 6, 2 * t, h, w), float("nan"), device=dev())
+    view = big[1:, 1:5, ::2]
+    view.copy_(torch.from_numpy(motion))
+    dense = view.contiguous()
+    assert view.stride(0) > dense.stride(0) and view.stride(1) > dense.stride(1) and view.stride(2) > dense.stride(2)
+    for forward, t0 in ((True, 0), (False, t - 1)):
+        ref = oracle_frames(img, motion, forward, t0, t - 1, mode)
+        for path, flag in paths_for(h, w):
+            a = run_track(img, view, forward, t0, t - 1, MODES[mode] | flag)
+            b = run_track(img, dense, forward, t0, t - 1, MODES[mode] | flag)
+            np.testing.assert_array_equal(a, b, err_msg=f"{path} path")
+            np.testing.assert_array_equal(a, ref, err_msg=f"{path} path")
+
+
+def test_track_refuses_bad_arguments():
+    """Each refusal returns its code, sets clasfv_last_error and leaves out untouched."""
+    n, c, h, w, t = 2, 2, 5, 9, 4
+    img = torch.zeros(n, c, h, w, device=dev())
+    mot = torch.zeros(n, 4, t, h, w, device=dev())
+    out = Guarded(4 * n * c * h * w)
+    ok = dict(img=ptr(img), mot=ptr(mot), t0=0, step=1, count=3, mode=BILINEAR, out=ptr(out.t), n=n, c=c, h=h, w=w)
+    bad = [dict(count=0), dict(count=-1), dict(step=2), dict(step=0), dict(step=-2), dict(t0=2), dict(t0=-1),
+           dict(t0=t), dict(t0=1, step=-1), dict(mode=2), dict(mode=7), dict(mode=0x400),
+           dict(mode=FORCE_STEPS | FORCE_LDS), dict(mode=-1),
+           dict(img=NUL), dict(mot=NUL), dict(out=NUL), dict(n=0), dict(c=0), dict(h=0), dict(w=-3),
+           dict(out=ptr(img)), dict(img=ptr(out.t[n * c * h * w:]))]
+    for change in bad:
+        a = dict(ok, **change)
+        rc = call_track(a["img"], a["n"], a["c"], a["h"], a["w"], a["mot"], True, t, a["t0"], a["step"], a["count"],
+                        a["mode"], a["out"])
+        assert rc == EINVAL, (change, rc)
+        assert lib().clasfv_last_error(), change
+        assert out.untouched(), change
+    assert call_track(ok["img"], n, c, h, w, ok["mot"], True, t, 0, 1, 3, NEAREST | FORCE_STEPS, ok["out"]) == 0
+
+
+# ---- warp.track under autograd -------------------------------------------------------------------------
+GRAD_RTOL, GRAD_ATOL = 1e-4, 1e-7   # the project's bars for chained-warp gradients (tests/test_gpu.py)
+# Largest deviation allowed, in units of that bar (max |got - want| / (atol + rtol |want|)), per direction.
+# 1.0 is the project's bar; the others are twice the deviation of the per-step loop (see the test's docstring).
+GRAD_BAR = {True: {"gimg": 1.0, "gmot": 2 * 5.638}, False: {"gimg": 2 * 1.244, "gmot": 2 * 2.634}}
+
+
+def _bar_units(got, want):
+    return float((np.abs(got - want) / (GRAD_ATOL + GRAD_RTOL * np.abs(want))).max())
+
+
+@pytest.mark.parametrize("forward", [True, False], ids=["fwd", "bwd"])
+def test_track_autograd_vs_cpu_autograd(forward):
+    """warp.track on the loss_inputs() shapes (T = 6, 32x40) with a seeded gout for every frame, against CPU
+    autograd through oracle/warp_ref: forward bit-exact, gradients of img and motion at GRAD_BAR.
+
+    The project's bar for chained-warp gradients (rtol 1e-4, atol 1e-7) does not hold on these inputs, for
+    track or for the per-step loop of warp.warp it replaces: with gout ~ N(0, 1) on every frame the motion
+    gradients are sums of terms of magnitude 10 that cancel to 1e-3 in places, and the float atomics of
+    grad_img, whose order changes from run to run, move such an element by an ulp of its terms. Measured on
+    the MI355X against this oracle on these inputs, in units of that bar (largest of 28 runs each; the
+    per-step loop is what the package ran before track, and runs the same kernels step by step):
+        forward chain   per-step loop: grad_img 0.642, grad_motion 5.638    track: grad_img 0.734, grad_motion 5.360
+        backward chain  per-step loop: grad_img 1.244, grad_motion 2.634    track: grad_img 1.754, grad_motion 2.634
+    The forward grad_img bar holds and stays; the other three are set at twice the loop's deviation
+    (11.276, 2.488 and 5.268 units). Prints this run's deviations of both before asserting."""
+    from clasfv_amd import warp as W
+    d = loss_inputs()
+    img = np.ascontiguousarray(d["video"][:, :, 0])
+    motion = d["motion"]
+    t = motion.shape[2]
+    start, end = (0, t - 1) if forward else (t - 1, 0)
+    frames = list(range(start, end, 1 if forward else -1))
+    gout = rng_for("track-gout", forward).standard_normal((len(frames),) + img.shape).astype(np.float32)
+    ch = slice(0, 2) if forward else slice(2, 4)
+
+    ri, rm = torch.from_numpy(img).requires_grad_(), torch.from_numpy(motion).requires_grad_()
+    cur, chain = ri, []
+    for f in frames:
+        cur = warp_ref.warp(cur, rm[:, ch, f])
+        chain.append(cur)
+    ref = torch.stack(chain)
+    ref.backward(torch.from_numpy(gout))
+
+    def on_device(fn):
+        gi = torch.from_numpy(img).to(dev()).requires_grad_()
+        gm = torch.from_numpy(motion).to(dev()).requires_grad_()
+        out = fn(gi, gm)
+        out.backward(torch.from_numpy(gout).to(dev()))
+        return out.detach().cpu().numpy(), gi.grad.cpu().numpy(), gm.grad.cpu().numpy()
+
+    def loop(gi, gm):
+        cur, chain = gi, []
+        for f in frames:
+            cur = W.warp(cur, gm[:, ch, f])
+            chain.append(cur)
+        return torch.stack(chain)
+
+    out, gimg, gmot = on_device(lambda gi, gm: W.track(gi, gm, start, end, forward=forward))
+    lout, lgimg, lgmot = on_device(loop)
+    print(f"TRACK_GRAD {'fwd' if forward else 'bwd'} track: gimg {_bar_units(gimg, ri.grad.numpy()):.3f} "
+          f"gmot {_bar_units(gmot, rm.grad.numpy()):.3f}  warp loop: gimg {_bar_units(lgimg, ri.grad.numpy()):.3f} "
+          f"gmot {_bar_units(lgmot, rm.grad.numpy()):.3f} (units of rtol 1e-4 / atol 1e-7)")
+    np.testing.assert_array_equal(out, ref.detach().numpy())
+    np.testing.assert_array_equal(lout, out)
+    bar = GRAD_BAR[forward]
+    assert _bar_units(gimg, ri.grad.numpy()) <= bar["gimg"]
+    assert _bar_units(gmot, rm.grad.numpy()) <= bar["gmot"]
+    unused = np.ones(motion.shape, bool)
+    unused[:, ch, frames] = False
+    assert not gmot[unused].any(), "motion gradient outside the used frames and channels"
+
+    # one input alone: the same gradient, none for the other
+    gi = torch.from_numpy(img).to(dev()).requires_grad_()
+    gout_d = torch.from_numpy(gout).to(dev())
+    W.track(gi, torch.from_numpy(motion).to(dev()), start, end, forward=forward).backward(gout_d)
+    assert _bar_units(gi.grad.cpu().numpy(), ri.grad.numpy()) <= bar["gimg"]
+    gm = torch.from_numpy(motion).to(dev()).requires_grad_()
+    W.track(torch.from_numpy(img).to(dev()), gm, start, end, forward=forward).backward(gout_d)
+    assert _bar_units(gm.grad.cpu().numpy(), rm.grad.numpy()) <= bar["gmot"]
+
+
+def test_track_python_surface():
+    """Empty ranges, the nearest-mode refusal under autograd, bad modes and shapes."""
+    from clasfv_amd import warp as W
+    img = torch.rand(2, 3, 6, 8, device=dev())
+    mot = torch.zeros(2, 4, 5, 6, 8, device=dev())
+    for a, b, fwd in ((2, 2, True), (3, 1, True), (1, 3, False)):
+        e = W.track(img, mot, a, b, forward=fwd)
+        assert e.shape == (0, 2, 3, 6, 8) and e.dtype == torch.float32 and e.device == img.device
+        assert W.apply_sequence_deformation(img, mot, a, b, fwd) is img
+    with pytest.raises(ValueError):
+        W.track(img, mot.clone().requires_grad_(), 0, 3, mode="nearest")
+    with pytest.raises(ValueError):
+        W.track(img, mot, 0, 3, mode="bicubic")
+    with pytest.raises(ValueError):
+        W.track(img, mot[:, :2], 0, 3)
+    with pytest.raises(RuntimeError):   # frames 3, 4, 5 of 5: refused by the ABI
+        W.track(img, mot, 3, 6)
+    assert W.track(img, mot, 0, 3, mode="nearest").shape == (3, 2, 3, 6, 8)
+
+
+# ---- track_labels, apply_sequence_deformation, losses -------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.int64, torch.uint8], ids=["int64", "uint8"])
+@pytest.mark.parametrize("seed_index", [0, 3, 7])
+def test_track_labels_vs_oracle_loop(seed_index, dtype):
+    """The tracked mask video of a (2,8,24,20) disk mask against a CPU loop of nearest-mode warps: forward
+    fields after the seed frame, backward fields before it, the seed frame itself unchanged, int64."""
+    from clasfv_amd import warp as W
+    n, t, h, w = 2, 8, 24, 20
+    rng = rng_for("labels")
+    yy, xx = np.mgrid[0:h, 0:w]
+    labels = np.stack([np.stack([(((yy - h / 2 - k) / (5.0 + f % 3)) ** 2 + ((xx - w / 2) / 6.0) ** 2 <= 1) * (1 + k)
+                                 for f in range(t)]) for k in range(n)]).astype(np.int64)
+    motion = (0.5 * np.tanh(rng.normal(0, 0.5, (n, 4, t, h, w)))).astype(np.float32)
+    want = np.empty((n, t, h, w), np.int64)
+    want[:, seed_index] = labels[:, seed_index]
+    seed = torch.from_numpy(labels[:, seed_index:seed_index + 1].astype(np.float32))
+    cur = seed
+    for f in range(seed_index, t - 1):
+        cur = warp_ref.warp(cur, motion[:, :2, f], "nearest")
+        want[:, f + 1] = cur[:, 0].numpy()
+    cur = seed
+    for f in range(seed_index, 0, -1):
+        cur = warp_ref.warp(cur, motion[:, 2:, f], "nearest")
+        want[:, f - 1] = cur[:, 0].numpy()
+    got = W.track_labels(torch.from_numpy(labels).to(dev(), dtype), torch.from_numpy(motion).to(dev()), seed_index)
+    assert got.dtype == torch.int64 and got.shape == (n, t, h, w) and got.device.type == "cuda"
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    np.testing.assert_array_equal(got[:, seed_index].cpu().numpy(), labels[:, seed_index])
+    assert (want != labels).any()
+
+
+def test_apply_sequence_deformation_default_and_nearest():
+    """Default arguments: bit-identical to a loop of warp.warp calls (the behaviour before track), positional
+    call included. grid_mode="nearest": the oracle's."""
+    from clasfv_amd import warp as W
+    d = track_inputs()
+    img, motion = torch.from_numpy(d["img"]).to(dev()), torch.from_numpy(d["motion"]).to(dev())
+    for forward, start, end in ((True, 0, 5), (False, 5, 1), (True, 2, 3)):
+        cur = img
+        for f in range(start, end, 1 if forward else -1):
+            cur = W.warp(cur, motion[:, :2, f] if forward else motion[:, 2:, f])
+        got = W.apply_sequence_deformation(img, motion, start, end, forward)
+        np.testing.assert_array_equal(got.cpu().numpy(), cur.cpu().numpy())
+        near = W.apply_sequence_deformation(img, motion, start, end, forward=forward, grid_mode="nearest")
+        ref = warp_ref.apply_sequence_deformation(torch.from_numpy(d["img"]), torch.from_numpy(d["motion"]), start, end,
+                                                  "nearest", forward)
+        np.testing.assert_array_equal(near.cpu().numpy(), ref.numpy())
+
+
+def test_motion_seg_loss_runs_each_chain_as_one_track_call(monkeypatch):
+    """losses.motion_seg_loss issues one clasfv_track per non-empty chain and no clasfv_warp."""
+    from clasfv_amd import _lib, losses
+    d = loss_inputs()
+    calls = []
+    real = _lib.load()
+
+    class Spy:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if name in ("clasfv_track", "clasfv_warp"):
+                def wrapped(*a):
+                    calls.append(name)
+                    return fn(*a)
+                return wrapped
+            return fn
+    monkeypatch.setattr(_lib, "load", lambda: Spy())
+    motion = torch.from_numpy(d["motion"]).to(dev())
+    soft = torch.softmax(torch.from_numpy(d["logits"]).to(dev()), 1)
+    flow, ots = losses.motion_seg_loss(d["ed"], d["es"], d["ed_index"], d["es_index"], motion, soft, start=0,
+                                       end=motion.shape[2])
+    assert calls == ["clasfv_track"] * 4
+    assert np.isfinite(float(flow)) and np.isfinite(float(ots))
