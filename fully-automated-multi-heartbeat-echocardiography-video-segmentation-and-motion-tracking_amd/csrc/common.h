@@ -44,7 +44,8 @@ __device__ inline int fdiv(int n, FastDiv f) { return (int)((__umulhi((unsigned)
 //   k = ((kt*KH + kh)*KW + kw)*Cin + c           (tap-major, channel-minor)
 struct ConvParams {
   const void* x;      // [N][Ti][Hi][Wi][Cin], fp32 or bf16 (in_bf16)
-  const void* w;      // [Cout_alloc][Kp], zero padded, same dtype as x
+  const void* w;      // the weight image of the kernel launched (engine.hip, kKernels); the implicit GEMMs':
+                      // [Cout_alloc][Kp], zero padded, same dtype as x
   const float* bias;  // [Cout_alloc] or nullptr
   const void* res;    // [M][Cout] or nullptr (may alias y), dtype of y
   void* y;            // [M][Cout], fp32 or bf16 (out_bf16)
@@ -58,16 +59,18 @@ struct ConvParams {
   int stem;           // fp32 4-channel input (3 + pad): register-staged kernel, per-float4 tap decode
   int in_bf16, out_bf16;
   // 8-channel-blocked activations [C/8][N*T*H*W][8] instead of channels-last (fp32 only): the
-  // mid tensor of a Conv2Plus1D between a stride-1 spatial producer (conv_wino_q on 8x8-pixel
-  // patches and conv_stem_f32 write y_c8) and the temporal Winograd consumer (conv_winot5 reads x_c8), whose
-  // 8-channel chunks then read whole 128-B lines instead of 32 B of every pixel.
+  // mid tensor of a Conv2Plus1D between a stride-1 spatial producer (the kernels engine.hip's kKernels
+  // marks as writing it: the F(4x4,3x3) ones, conv_wino_q, conv_stem_f32 and conv_stem_x3 write y_c8) and the
+  // temporal Winograd consumer (conv_winot, in its conv_winot5 form, reads x_c8), whose 8-channel chunks
+  // then read whole 128-B lines instead of 32 B of every pixel.
   int x_c8, y_c8;
   // Kernel-choice switches of the engine (CLASFV_VARIANT_* of include/clasfv.h, read from the
   // environment once at clasfv_create or set with clasfv_set_kernel_variants) and the tuning
   // overrides of the bf16 patch kernel's N tile (0: automatic).
   int vflags, patch_nt;
-  // Split-K (conv_winot5 on grids smaller than the chip): n_split > 1 blocks per output tile, each
-  // over a contiguous range of input-channel chunks, write their partial sums to part[split] (fp32,
+  // Split-K (conv_winot, conv_dma_x3 and conv_dma on grids smaller than the chip; winot_split_for,
+  // dma_split_for): n_split > 1 blocks per output tile, each over a contiguous range of K (input-channel
+  // chunks for conv_winot), write their partial sums to part[split] (fp32,
   // [n_split][M][Cout]); a second pass adds them in split order with bias, residual and ReLU.
   float* part;
   int n_split;

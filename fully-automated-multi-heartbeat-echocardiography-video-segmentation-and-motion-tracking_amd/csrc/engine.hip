@@ -78,15 +78,30 @@ struct Conv {
   int stem = 0, in_bf16 = 0, out_bf16 = 0;
   void* dw = nullptr;     // weights, dtype of the conv's input
   float* db = nullptr;    // folded-BN bias (fp32)
-  float* dwino = nullptr;  // Winograd F(2x2,3x3) transformed weights (fp32 stride-1 1x3x3 convs)
-  float* dwino4 = nullptr;  // Winograd F(4x4,3x3) transformed weights (the same convs, cout_p % 48 == 0)
-  float* dwino4w = nullptr;  // the same for conv_wino4w's wide output-channel blocks (wino4w_ntn(cout_p) > 0)
-  float* dwino4r = nullptr;  // the same values in conv_wino4r's (12 row waves) order
-  float* dwinot = nullptr;  // Winograd F(4,3)-in-time transformed weights (fp32 stride-1 3x1x1 convs)
+  void* dwino = nullptr;  // Winograd F(2x2,3x3) transformed weights (fp32 stride-1 1x3x3 convs)
+  void* dwino4 = nullptr;  // Winograd F(4x4,3x3) transformed weights (the same convs, cout_p % 48 == 0)
+  void* dwino4w = nullptr;  // the same for conv_wino4w's wide output-channel blocks (wino4w_ntn(cout_p) > 0)
+  void* dwino4r = nullptr;  // the same values in conv_wino4r's (12 row waves) order
+  void* dwinot = nullptr;  // Winograd F(4,3)-in-time transformed weights (fp32 stride-1 3x1x1 convs)
   void* dws16 = nullptr;    // bf16 stem weights, hi and lo images [64][7 kh][8 kw][4 c] (bf16 engines);
                             // fp32 engines: hi, mid and lo images [48][7][8][4] (conv_stem_x3)
   void* dx3 = nullptr;      // fp32 engines' implicit-GEMM convs: 3-piece bf16 image for conv_dma_x3
 };
+
+// Every weight image of a Conv; a kKernels row names the one its kernel takes as ConvParams::w.
+using ConvImage = void* Conv::*;
+constexpr ConvImage kConvImages[] = {&Conv::dw,      &Conv::dwino,  &Conv::dwino4, &Conv::dwino4w,
+                                     &Conv::dwino4r, &Conv::dwinot, &Conv::dws16,  &Conv::dx3};
+
+// Frees every device image of c and its bias, and nulls the pointers.
+void free_conv_images(Conv& c) {
+  for (ConvImage img : kConvImages) {
+    (void)hipFree(c.*img);
+    c.*img = nullptr;
+  }
+  (void)hipFree(c.db);
+  c.db = nullptr;
+}
 
 // fp32 stride-1 3x1x1 convs run on the fused temporal Winograd kernel, fp32 stride-1 1x3x3 convs on
 // the fused spatial one (CLASFV_VARIANT_NO_WINOGRAD: both on the direct implicit GEMM).
@@ -102,46 +117,55 @@ bool use_wino(const Conv& c, bool bf16, int vflags) {
          c.sw == 1 && c.cin_p % 16 == 0 && c.cout_p % 48 == 0;
 }
 
+// Every CLASFV_VARIANT_* bit of include/clasfv.h with the environment variable that sets it: a switch
+// is on when its variable is set to anything, a `zero_form` one when its variable starts with '0'.
+struct VariantSwitch {
+  int bit;
+  const char* env;
+  bool zero_form;
+};
+constexpr VariantSwitch kVariants[] = {
+    {CLASFV_VARIANT_NO_WINOGRAD, "CLASFV_WINOGRAD", true},
+    {CLASFV_VARIANT_NO_WINO_PATCH, "CLASFV_NO_WINO_PATCH", false},
+    {CLASFV_VARIANT_WINOT_REFERENCE, "CLASFV_WINOT_REFERENCE", false},
+    {CLASFV_VARIANT_NO_C8, "CLASFV_NO_C8", false},
+    {CLASFV_VARIANT_NO_STEM_BF16, "CLASFV_NO_STEM_BF16", false},
+    {CLASFV_VARIANT_NO_PATCH_BF16, "CLASFV_NO_PATCH_BF16", false},
+    {CLASFV_VARIANT_NO_DECODER_BF16, "CLASFV_NO_DECODER_BF16", false},
+    {CLASFV_VARIANT_WINOT_NO_TS1, "CLASFV_WINOT_TS1", true},
+    {CLASFV_VARIANT_NO_SPLIT_K, "CLASFV_NO_SPLIT_K", false},
+    {CLASFV_VARIANT_NO_WINO4, "CLASFV_NO_WINO4", false},
+    {CLASFV_VARIANT_NO_DECODER_X3, "CLASFV_NO_DECODER_X3", false},
+    {CLASFV_VARIANT_NO_DMA_X3, "CLASFV_NO_DMA_X3", false},
+    {CLASFV_VARIANT_NO_STEM_X3, "CLASFV_NO_STEM_X3", false},
+    {CLASFV_VARIANT_NO_WINO4W, "CLASFV_NO_WINO4W", false},
+    {CLASFV_VARIANT_NO_PATCH32, "CLASFV_NO_PATCH32", false},
+    {CLASFV_VARIANT_NO_PROJ_X3, "CLASFV_NO_PROJ_X3", false},
+    {CLASFV_VARIANT_NO_WINO4R, "CLASFV_NO_WINO4R", false},
+    {CLASFV_VARIANT_NO_DMA_BUF, "CLASFV_NO_DMA_BUF", false},
+    {CLASFV_VARIANT_W4R_CACHED_STORES, "CLASFV_W4R_CACHED_STORES", false},
+    {CLASFV_VARIANT_PATCH32_CACHED_STORES, "CLASFV_PATCH32_CACHED_STORES", false},
+    {CLASFV_VARIANT_NO_DMA_W, "CLASFV_NO_DMA_W", false},
+    {CLASFV_VARIANT_NO_TWALK, "CLASFV_NO_TWALK", false},
+};
+
 // Kernel-variant flags and tuning overrides from the environment (read once, at clasfv_create).
 int env_variants() {
-  auto on = [](const char* n) { return getenv(n) != nullptr; };
-  const char* w = getenv("CLASFV_WINOGRAD");
-  const char* ts1 = getenv("CLASFV_WINOT_TS1");
   int f = 0;
-  if (w && w[0] == '0') f |= CLASFV_VARIANT_NO_WINOGRAD;
-  if (on("CLASFV_NO_WINO_PATCH")) f |= CLASFV_VARIANT_NO_WINO_PATCH;
-  if (on("CLASFV_WINOT_REFERENCE")) f |= CLASFV_VARIANT_WINOT_REFERENCE;
-  if (on("CLASFV_NO_C8")) f |= CLASFV_VARIANT_NO_C8;
-  if (on("CLASFV_NO_STEM_BF16")) f |= CLASFV_VARIANT_NO_STEM_BF16;
-  if (on("CLASFV_NO_PATCH_BF16")) f |= CLASFV_VARIANT_NO_PATCH_BF16;
-  if (on("CLASFV_NO_DECODER_BF16")) f |= CLASFV_VARIANT_NO_DECODER_BF16;
-  if (ts1 && ts1[0] == '0') f |= CLASFV_VARIANT_WINOT_NO_TS1;
-  if (on("CLASFV_NO_SPLIT_K")) f |= CLASFV_VARIANT_NO_SPLIT_K;
-  if (on("CLASFV_NO_WINO4")) f |= CLASFV_VARIANT_NO_WINO4;
-  if (on("CLASFV_NO_DECODER_X3")) f |= CLASFV_VARIANT_NO_DECODER_X3;
-  if (on("CLASFV_NO_DMA_X3")) f |= CLASFV_VARIANT_NO_DMA_X3;
-  if (on("CLASFV_NO_STEM_X3")) f |= CLASFV_VARIANT_NO_STEM_X3;
-  if (on("CLASFV_NO_WINO4W")) f |= CLASFV_VARIANT_NO_WINO4W;
-  if (on("CLASFV_NO_PATCH32")) f |= CLASFV_VARIANT_NO_PATCH32;
-  if (on("CLASFV_NO_PROJ_X3")) f |= CLASFV_VARIANT_NO_PROJ_X3;
-  if (on("CLASFV_NO_WINO4R")) f |= CLASFV_VARIANT_NO_WINO4R;
-  if (on("CLASFV_NO_DMA_BUF")) f |= CLASFV_VARIANT_NO_DMA_BUF;
-  if (on("CLASFV_W4R_CACHED_STORES")) f |= CLASFV_VARIANT_W4R_CACHED_STORES;
-  if (on("CLASFV_PATCH32_CACHED_STORES")) f |= CLASFV_VARIANT_PATCH32_CACHED_STORES;
-  if (on("CLASFV_NO_DMA_W")) f |= CLASFV_VARIANT_NO_DMA_W;
-  if (on("CLASFV_NO_TWALK")) f |= CLASFV_VARIANT_NO_TWALK;
+  for (const VariantSwitch& v : kVariants) {
+    const char* e = getenv(v.env);
+    if (e && (!v.zero_form || e[0] == '0')) f |= v.bit;
+  }
   return f;
 }
 
-// every CLASFV_VARIANT_* bit of include/clasfv.h (the retired bits are rejected)
-constexpr int kVariantMask = CLASFV_VARIANT_NO_WINOGRAD | CLASFV_VARIANT_NO_WINO_PATCH | CLASFV_VARIANT_WINOT_REFERENCE |
-                             CLASFV_VARIANT_NO_C8 | CLASFV_VARIANT_NO_STEM_BF16 | CLASFV_VARIANT_NO_PATCH_BF16 |
-                             CLASFV_VARIANT_NO_DECODER_BF16 | CLASFV_VARIANT_WINOT_NO_TS1 | CLASFV_VARIANT_NO_SPLIT_K |
-                             CLASFV_VARIANT_NO_WINO4 | CLASFV_VARIANT_NO_DECODER_X3 | CLASFV_VARIANT_NO_DMA_X3 |
-                             CLASFV_VARIANT_NO_STEM_X3 | CLASFV_VARIANT_NO_WINO4W | CLASFV_VARIANT_NO_PATCH32 |
-                             CLASFV_VARIANT_NO_PROJ_X3 | CLASFV_VARIANT_NO_WINO4R | CLASFV_VARIANT_NO_DMA_BUF |
-                             CLASFV_VARIANT_W4R_CACHED_STORES | CLASFV_VARIANT_PATCH32_CACHED_STORES |
-                             CLASFV_VARIANT_NO_DMA_W | CLASFV_VARIANT_NO_TWALK;
+// the bits clasfv_set_kernel_variants accepts (the retired bits are rejected)
+constexpr int variant_mask() {
+  int m = 0;
+  for (const VariantSwitch& v : kVariants) m |= v.bit;
+  return m;
+}
+constexpr int kVariantMask = variant_mask();
 
 int env_int(const char* name) {
   const char* e = getenv(name);
@@ -306,7 +330,8 @@ void bn_scale_shift(clasfv_engine* e, const std::string& bn, int c, std::vector<
   }
 }
 
-int upload(const std::vector<float>& h, float** d) {
+template <class T>  // T: float, or void for a Conv image
+int upload(const std::vector<float>& h, T** d) {
   HIP_TRY(hipMalloc(d, h.size() * sizeof(float)));
   HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
   return CLASFV_OK;
@@ -337,7 +362,7 @@ int upload_conv(Conv& c, F wsrc, const std::vector<double>& scale, const std::ve
     for (int tap = 0; tap < taps; ++tap)
       for (int ci = 0; ci < c.cin; ++ci)
         w[(size_t)o * c.Kp + (size_t)tap * c.cin_p + ci] = (float)((double)wsrc(o, ci, tap) * scale[o]);
-  int rc = c.in_bf16 ? upload_bf16(w, &c.dw) : upload(w, reinterpret_cast<float**>(&c.dw));
+  int rc = c.in_bf16 ? upload_bf16(w, &c.dw) : upload(w, &c.dw);
   if (rc) return rc;
   if (!c.in_bf16 && !c.stem && c.Kp % 16 == 0) {  // conv_dma_x3's split image of the same weights
     std::vector<uint16_t> x3(dma_x3_weight_elems(c.cout_alloc, c.Kp));
@@ -353,6 +378,182 @@ int upload_conv(Conv& c, F wsrc, const std::vector<double>& scale, const std::ve
   return rc;
 }
 
+// BN-folded weights w[cout][cin][taps] of c as double products, unrounded: what the Winograd weight
+// transforms take (upload_conv rounds the same products to float first, on purpose).
+std::vector<double> folded_weights(const Conv& c, const std::vector<float>& w, const std::vector<double>& s, int taps) {
+  const size_t per_o = (size_t)c.cin * taps;
+  std::vector<double> wf((size_t)c.cout * per_o);
+  for (int o = 0; o < c.cout; ++o)
+    for (size_t i = 0; i < per_o; ++i) wf[o * per_o + i] = (double)w[o * per_o + i] * s[o];
+  return wf;
+}
+
+// The spatial Winograd images of a 1x3x3 conv (use_wino), each where its kernel has a tile for the widths.
+int upload_wino_images(Conv& c, const std::vector<float>& w, const std::vector<double>& s) {
+  const std::vector<double> wf = folded_weights(c, w, s, 9);
+  int rc;
+  std::vector<float> u((size_t)16 * c.cin_p * c.cout_p);
+  wino_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u.data());
+  if ((rc = upload(u, &c.dwino))) return rc;
+  if (c.cout_p % 48 == 0 && c.cin_p % 8 == 0) {
+    std::vector<float> u4(wino4_weight_floats(c.cin_p, c.cout_p));
+    wino4_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u4.data());
+    if ((rc = upload(u4, &c.dwino4))) return rc;
+  }
+  if (c.cin_p % 8 == 0 && wino4w_weight_floats(c.cin_p, c.cout_p)) {
+    std::vector<float> uw(wino4w_weight_floats(c.cin_p, c.cout_p));
+    wino4w_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, uw.data());
+    if ((rc = upload(uw, &c.dwino4w))) return rc;
+  }
+  if (c.cin_p % 8 == 0 && wino4r_weight_floats(c.cin_p, c.cout_p)) {
+    std::vector<float> ur(wino4r_weight_floats(c.cin_p, c.cout_p));
+    wino4r_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, ur.data());
+    if ((rc = upload(ur, &c.dwino4r))) return rc;
+  }
+  return CLASFV_OK;
+}
+
+// The temporal Winograd image of a 3x1x1 conv (use_winot).
+int upload_winot_image(Conv& c, const std::vector<float>& w, const std::vector<double>& s) {
+  const std::vector<double> wf = folded_weights(c, w, s, 3);
+  std::vector<float> u((size_t)6 * c.cin_p * c.cout_p);
+  winot_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u.data());
+  return upload(u, &c.dwinot);
+}
+
+// fn(k, raw weight, its output channel's BN scale) for every 7x7 tap of the stem, k its offset in a
+// [cout_p][7 kh][8 kw][4 c] image: the K order conv_stem_x3 and conv_stem_bf16 share.
+template <class F>
+void for_stem_taps(const Conv& c, const std::vector<float>& w, const std::vector<double>& s, F fn) {
+  for (int o = 0; o < c.cout; ++o)
+    for (int ci = 0; ci < c.cin; ++ci)
+      for (int kh = 0; kh < 7; ++kh)
+        for (int kw = 0; kw < 7; ++kw)
+          fn((((size_t)o * 7 + kh) * 8 + kw) * 4 + ci, w[((size_t)o * c.cin + ci) * 49 + kh * 7 + kw], s[o]);
+}
+
+// The stem's split-bf16 images (Conv::dws16); each kernel's pieces keep their own rounding.
+int upload_stem_images(Conv& c, const std::vector<float>& w, const std::vector<double>& s, bool bf16) {
+  if (!c.stem || c.kh != 7 || c.kw != 7 || c.cin > 4) return CLASFV_OK;
+  if (!bf16 && c.cout_p == 48) {  // conv_stem_x3's pieces
+    const size_t img = (size_t)48 * 7 * 8 * 4;
+    std::vector<float> ws(3 * img, 0.f);  // hi, mid, lo: bf16 of the remainder, in double
+    for_stem_taps(c, w, s, [&](size_t k, float wv, double scale) {
+      double r = (double)(float)((double)wv * scale);
+      for (int pc = 0; pc < 3; ++pc) {
+        const uint32_t hb = (uint32_t)to_bf16((float)r) << 16;
+        float f;
+        memcpy(&f, &hb, 4);
+        ws[pc * img + k] = f;
+        r -= f;
+      }
+    });
+    return upload_bf16(ws, &c.dws16);
+  }
+  if (bf16 && c.cout_p == 64) {  // conv_stem_bf16's K order
+    const size_t img = (size_t)64 * 7 * 8 * 4;
+    std::vector<float> ws(2 * img, 0.f);  // hi image, then lo = bf16(w - hi)
+    for_stem_taps(c, w, s, [&](size_t k, float wv, double scale) {
+      const float v = (float)((double)wv * scale);
+      const uint32_t hb = (uint32_t)to_bf16(v) << 16;
+      float hi;
+      memcpy(&hi, &hb, 4);
+      ws[k] = hi;
+      ws[img + k] = v - hi;
+    });
+    return upload_bf16(ws, &c.dws16);
+  }
+  return CLASFV_OK;
+}
+
+// Every device image of one backbone conv, BN folded, for the engine's compute dtype and variants.
+int finalize_conv(clasfv_engine* h, Conv& c, bool bf16) {
+  free_conv_images(c);
+  std::vector<double> s, t;
+  bn_scale_shift(h, c.bn, c.cout, s, t);
+  const auto& w = P(h, c.w + ".weight");
+  const int taps = c.kt * c.kh * c.kw;
+  const int cin = c.cin;
+  int rc = upload_conv(
+      c, [&](int o, int ci, int tap) { return w[((size_t)o * cin + ci) * taps + tap]; }, s, t, true);
+  if (!rc && use_wino(c, bf16, h->tune.vflags)) rc = upload_wino_images(c, w, s);
+  if (!rc) rc = upload_stem_images(c, w, s, bf16);
+  if (!rc && use_winot(c, bf16, h->tune.vflags)) rc = upload_winot_image(c, w, s);
+  return rc;
+}
+
+// comb_1 + BN1 folded, split per tap (concat order stem, layer1, layer2, layer3, layer4)
+int finalize_projections(clasfv_engine* h) {
+  std::vector<double> s, t;
+  bn_scale_shift(h, "comb_batch_norm_1", 64, s, t);
+  const auto& w1 = P(h, "comb_1_layer.weight");
+  const std::vector<double> zero(64, 0.0);
+  const int col0[5] = {0, 64, 128, 256, 512};
+  for (int i = 0; i < 5; ++i) {
+    if (i == 1) continue;  // folded into the dual proj[0]
+    Conv& c = h->proj[i];
+    free_conv_images(c);
+    const int o0 = col0[i];
+    Conv tmp = c;  // upload_conv walks cin: give it the concatenated width
+    tmp.cin = tmp.cin_p = c.cin + c.cin2;
+    int rc = upload_conv(
+        tmp, [&](int o, int ci, int) { return w1[(size_t)o * 1024 + o0 + ci]; }, s, zero, false);
+    if (rc) return rc;
+    c.dw = tmp.dw;
+    c.dx3 = tmp.dx3;
+  }
+  return CLASFV_OK;
+}
+
+// The decoder's own weights: comb_1's bias through BN1, comb_2 + BN2 folded, and the two heads as one
+// 8-row matrix (seg0, seg1, mot0..mot3, 0, 0).
+int finalize_decoder(clasfv_engine* h) {
+  std::vector<double> s, t;
+  bn_scale_shift(h, "comb_batch_norm_1", 64, s, t);
+  const auto& bias1 = P(h, "comb_1_layer.bias");
+  std::vector<float> b1(64);
+  for (int o = 0; o < 64; ++o) b1[o] = (float)(s[o] * (double)bias1[o] + t[o]);
+  bn_scale_shift(h, "comb_batch_norm_2", 64, s, t);
+  const auto& w2 = P(h, "comb_2_layer.weight");
+  const auto& bias2 = P(h, "comb_2_layer.bias");
+  std::vector<float> w2f(64 * 64), b2(64);
+  for (int o = 0; o < 64; ++o) {
+    for (int k = 0; k < 64; ++k) w2f[o * 64 + k] = (float)((double)w2[o * 64 + k] * s[o]);
+    b2[o] = (float)(s[o] * (double)bias2[o] + t[o]);
+  }
+  const auto& ws = P(h, "segmentation_head.weight");
+  const auto& bs = P(h, "segmentation_head.bias");
+  const auto& wm = P(h, "motion_head.weight");
+  const auto& bm = P(h, "motion_head.bias");
+  std::vector<float> whf(8 * 64, 0.f), bhf(8, 0.f);
+  for (int k = 0; k < 64; ++k) {
+    whf[0 * 64 + k] = ws[k];
+    whf[1 * 64 + k] = ws[64 + k];
+    for (int m = 0; m < 4; ++m) whf[(2 + m) * 64 + k] = wm[m * 64 + k];
+  }
+  bhf[0] = bs[0];
+  bhf[1] = bs[1];
+  for (int m = 0; m < 4; ++m) bhf[2 + m] = bm[m];
+  for (float** d : {&h->b1, &h->w2, &h->b2, &h->wh, &h->bh}) {
+    (void)hipFree(*d);
+    *d = nullptr;
+  }
+  // W2 and the head weights as hi + mid + lo bf16 pieces in the X3 decoder's lane order
+  std::vector<uint16_t> w2x3(DECODER_X3_ELEMS);
+  decoder_x3_weights(w2f.data(), whf.data(), w2x3.data());
+  (void)hipFree(h->w2x3);
+  h->w2x3 = nullptr;
+  int rc = upload(b1, &h->b1);
+  if (!rc) rc = upload(w2f, &h->w2);
+  if (!rc && hipMalloc(&h->w2x3, w2x3.size() * sizeof(uint16_t)) != hipSuccess) rc = fail(CLASFV_EHIP, "hipMalloc");
+  if (!rc && hipMemcpy(h->w2x3, w2x3.data(), w2x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(CLASFV_EHIP, "hipMemcpy");
+  if (!rc) rc = upload(b2, &h->b2);
+  if (!rc) rc = upload(whf, &h->wh);
+  if (!rc) rc = upload(bhf, &h->bh);
+  return rc;
+}
+
 struct Shape5 {
   int n, t, h, w, c;
   size_t numel() const { return (size_t)n * t * h * w * c; }
@@ -364,50 +565,108 @@ double conv_gflop(const Conv& c, const Shape5& out) {
   return 2.0 * m * c.cout * (double)(c.cin + c.cin2) * c.kt * c.kh * c.kw * 1e-9;
 }
 
-// MFMA work one launch of kernel `kname` executes for conv c (2 FLOP per multiply-add issued to
-// the matrix cores, padded channels and partial tiles included): Winograd F(2x2,3x3) issues 16
-// products per 2x2 output tile and (input, output) channel pair instead of 36, F(2x4,3x3) 24 per
-// 2x4 tile instead of 72, F(4,3) in time 6 per 4 frames instead of 12; the implicit GEMMs issue
-// ceil(M / BM) * BM rows x cout_p x Kp.
-double conv_exec_gflop(const Conv& c, const Shape5& out, const char* kname) {
+// MFMA work one launch of a kernel executes for conv c (2 FLOP per multiply-add issued to the
+// matrix cores, padded channels and partial tiles included), one function per formula (kKernels):
+// Winograd F(2x2,3x3) issues 16 products per 2x2 output tile and (input, output) channel pair
+// instead of 36, F(2x4,3x3) 24 per 2x4 tile instead of 72, F(4,3) in time 6 per 4 frames instead of
+// 12; the implicit GEMMs issue ceil(M / BM) * BM rows x cout_p x Kp.
+// F(4x4,3x3): 36 products per 4x4 tile and channel pair, 16-tile groups (counted by the kernels' files)
+ConvParams wino4_exec_shape(const Conv& c, const Shape5& out) {
+  ConvParams p{};
+  p.N = out.n, p.Ti = p.To = out.t, p.Hi = p.Ho = out.h, p.Wi = p.Wo = out.w;
+  p.Cin = c.cin_p, p.Cout = c.cout_p;
+  return p;
+}
+double xg_wino4r(const Conv& c, const Shape5& out) { return wino4r_exec_gflop(wino4_exec_shape(c, out)); }
+double xg_wino4w(const Conv& c, const Shape5& out) { return wino4w_exec_gflop(wino4_exec_shape(c, out)); }
+double xg_wino4(const Conv& c, const Shape5& out) { return wino4_exec_gflop(wino4_exec_shape(c, out)); }
+double xg_wino(const Conv& c, const Shape5& out) {
   const double nt = (double)out.n * out.t;
   const double cc = (double)c.cin_p * c.cout_p;
-  if (!strcmp(kname, "conv_wino4") || !strcmp(kname, "conv_wino4w") || !strcmp(kname, "conv_wino4r")) {  // F(4x4,3x3): 36 products per 4x4
-    ConvParams p{};                                                           // tile and channel pair, 16-tile groups
-    p.N = out.n, p.Ti = p.To = out.t, p.Hi = p.Ho = out.h, p.Wi = p.Wo = out.w;
-    p.Cin = c.cin_p, p.Cout = c.cout_p;
-    return kname[10] == 'r' ? wino4r_exec_gflop(p) : kname[10] == 'w' ? wino4w_exec_gflop(p) : wino4_exec_gflop(p);
-  }
-  if (!strcmp(kname, "conv_wino_q") || !strcmp(kname, "conv_wino"))
-    return 2.0 * nt * ((out.h + 1) / 2) * ((out.w + 1) / 2) * 16.0 * cc * 1e-9;
-  if (!strcmp(kname, "conv_winot")) return 2.0 * out.n * (out.t / 4) * (double)out.h * out.w * 6.0 * cc * 1e-9;
-  // Split-bf16 ("x3") kernels of the fp32 engines run on the bf16 matrix pipe: their work is counted
-  // in that pipe's own products, six bf16 products per product of the fp32 GEMM they compute (the
-  // f32-MFMA kernels count f32 products), so each kernel's rate compares with the peak of the pipe it
-  // issues to (bench.py rates them against 2.5 PFLOP/s, the f32 ones against 157.3 TFLOP/s).
-  if (!strcmp(kname, "conv_stem_x3"))  // 6 x the fp32 GEMM (K = 7 rows x 8 taps x 4 channels)
-    return 6 * 2.0 * ceil((double)out.n * out.t * out.h * out.w / 256.0) * 256.0 * 48.0 * 224.0 * 1e-9;
-  if (!strcmp(kname, "conv_stem_bf16"))
-    return 3 * 2.0 * ceil((double)out.n * out.t * out.h * out.w / 256.0) * 256.0 * 64.0 * 224.0 * 1e-9;
-  if (!strcmp(kname, "conv_patch_bf16")) {  // frames x 64-pixel tiles: 2 x 8x8 for 1x3x3, 4 x 64 flat for 3x1x1
-    const int fr = c.kt == 1 ? 2 : 4;
-    const double px = c.kt == 1 ? (double)((out.h + 7) / 8 * 8) * ((out.w + 7) / 8 * 8)
-                                : (double)((out.h * out.w + 63) / 64 * 64);
-    return 2.0 * out.n * ((out.t + fr - 1) / fr * fr) * px * c.cout_p * (double)c.Kp * 1e-9;
-  }
-  if (!strcmp(kname, "conv_proj_x3"))  // 32-voxel items, 6 x the fp32 GEMM it computes
-    return 6 * 2.0 * ceil((double)out.n * out.t * out.h * out.w / 32.0) * 32.0 * c.cout_p * (double)c.Kp * 1e-9;
-  if (!strcmp(kname, "conv_twalk_bf16"))  // 32-pixel columns; 3T - 2 taps per output column (clip ends)
-    return 2.0 * out.n * ((out.h * out.w + 31) / 32 * 32) * (double)c.cout_p * c.cin_p * (3.0 * out.t - 2.0) * 1e-9;
-  if (!strcmp(kname, "conv_patch32_bf16"))  // 4 frames x 8x8-pixel tiles
-    return 2.0 * out.n * ((out.t + 3) / 4 * 4) * (double)((out.h + 7) / 8 * 8) * ((out.w + 7) / 8 * 8) * c.cout_p *
-           (double)c.Kp * 1e-9;
+  return 2.0 * nt * ((out.h + 1) / 2) * ((out.w + 1) / 2) * 16.0 * cc * 1e-9;
+}
+double xg_winot(const Conv& c, const Shape5& out) {
+  const double cc = (double)c.cin_p * c.cout_p;
+  return 2.0 * out.n * (out.t / 4) * (double)out.h * out.w * 6.0 * cc * 1e-9;
+}
+// Split-bf16 ("x3") kernels of the fp32 engines run on the bf16 matrix pipe: their work is counted
+// in that pipe's own products, six bf16 products per product of the fp32 GEMM they compute (the
+// f32-MFMA kernels count f32 products), so each kernel's rate compares with the peak of the pipe it
+// issues to (bench.py rates them against 2.5 PFLOP/s, the f32 ones against 157.3 TFLOP/s).
+double xg_stem_x3(const Conv&, const Shape5& out) {  // 6 x the fp32 GEMM (K = 7 rows x 8 taps x 4 channels)
+  return 6 * 2.0 * ceil((double)out.n * out.t * out.h * out.w / 256.0) * 256.0 * 48.0 * 224.0 * 1e-9;
+}
+double xg_stem_bf16(const Conv&, const Shape5& out) {
+  return 3 * 2.0 * ceil((double)out.n * out.t * out.h * out.w / 256.0) * 256.0 * 64.0 * 224.0 * 1e-9;
+}
+double xg_patch_bf16(const Conv& c, const Shape5& out) {  // frames x 64-pixel tiles: 2 x 8x8 for 1x3x3, 4 x 64 flat for 3x1x1
+  const int fr = c.kt == 1 ? 2 : 4;
+  const double px = c.kt == 1 ? (double)((out.h + 7) / 8 * 8) * ((out.w + 7) / 8 * 8)
+                              : (double)((out.h * out.w + 63) / 64 * 64);
+  return 2.0 * out.n * ((out.t + fr - 1) / fr * fr) * px * c.cout_p * (double)c.Kp * 1e-9;
+}
+double xg_proj_x3(const Conv& c, const Shape5& out) {  // 32-voxel items, 6 x the fp32 GEMM it computes
+  return 6 * 2.0 * ceil((double)out.n * out.t * out.h * out.w / 32.0) * 32.0 * c.cout_p * (double)c.Kp * 1e-9;
+}
+double xg_twalk_bf16(const Conv& c, const Shape5& out) {  // 32-pixel columns; 3T - 2 taps per output column (clip ends)
+  return 2.0 * out.n * ((out.h * out.w + 31) / 32 * 32) * (double)c.cout_p * c.cin_p * (3.0 * out.t - 2.0) * 1e-9;
+}
+double xg_patch32_bf16(const Conv& c, const Shape5& out) {  // 4 frames x 8x8-pixel tiles
+  return 2.0 * out.n * ((out.t + 3) / 4 * 4) * (double)((out.h + 7) / 8 * 8) * ((out.w + 7) / 8 * 8) * c.cout_p *
+         (double)c.Kp * 1e-9;
+}
+// conv_dma_x3: six bf16 products per product of the fp32 GEMM it computes (K padded to 32-deep pairs)
+double xg_dma_x3(const Conv& c, const Shape5& out) {
   const double m = (double)out.n * out.t * out.h * out.w;
-  // conv_dma_x3: six bf16 products per product of the fp32 GEMM it computes (K padded to 32-deep pairs)
-  if (!strcmp(kname, "conv_dma_x3"))
-    return 6 * 2.0 * (ceil(m / 128.0) * 128.0) * c.cout_p * (double)((c.Kp + 31) / 32 * 32) * 1e-9;
+  return 6 * 2.0 * (ceil(m / 128.0) * 128.0) * c.cout_p * (double)((c.Kp + 31) / 32 * 32) * 1e-9;
+}
+double xg_gemm(const Conv& c, const Shape5& out) {  // launch_conv's kernels: 128-row M tiles
+  const double m = (double)out.n * out.t * out.h * out.w;
   return 2.0 * (ceil(m / 128.0) * 128.0) * c.cout_p * (double)c.Kp * 1e-9;
 }
+
+// The conv kernels run_conv dispatches to. kKernels has one row per enumerator, in this order.
+enum Kernel {
+  K_WINO4R, K_WINO4W, K_WINO4, K_WINO_Q, K_WINO, K_STEM_BF16, K_STEM_X3, K_WINOT, K_PATCH_BF16, K_PATCH32_BF16,
+  K_TWALK_BF16, K_PROJ_X3, K_DMA_X3, K_STEM_F32, K_DMA_W, K_DMA
+};
+
+struct KernelInfo {
+  Kernel id;
+  const char* name;  // reported by clasfv_kernel_timing and clasfv_run_conv
+  ConvImage image;   // the Conv image the kernel takes as ConvParams::w
+  // 8-channel-blocked layout: kernels that may write it (y_c8) / read it (x_c8). Measured per
+  // producer (30 clips, profiles/r02j_*): stem and conv_wino_q (layer1, layer2) write the blocked
+  // layout at no cost while the temporal kernels after them gain 7-24 %; conv_wino (layer3) broke
+  // even and stays channels-last.
+  bool writes_c8, reads_c8;
+  double (*xgflop)(const Conv& c, const Shape5& out);  // MFMA work of one launch, see above
+};
+constexpr KernelInfo kKernels[] = {
+    {K_WINO4R, "conv_wino4r", &Conv::dwino4r, true, false, xg_wino4r},
+    {K_WINO4W, "conv_wino4w", &Conv::dwino4w, true, false, xg_wino4w},
+    {K_WINO4, "conv_wino4", &Conv::dwino4, true, false, xg_wino4},
+    {K_WINO_Q, "conv_wino_q", &Conv::dwino, true, false, xg_wino},
+    {K_WINO, "conv_wino", &Conv::dwino, false, false, xg_wino},
+    {K_STEM_BF16, "conv_stem_bf16", &Conv::dws16, false, false, xg_stem_bf16},
+    {K_STEM_X3, "conv_stem_x3", &Conv::dws16, true, false, xg_stem_x3},
+    {K_WINOT, "conv_winot", &Conv::dwinot, false, true, xg_winot},
+    {K_PATCH_BF16, "conv_patch_bf16", &Conv::dw, false, false, xg_patch_bf16},
+    {K_PATCH32_BF16, "conv_patch32_bf16", &Conv::dw, false, false, xg_patch32_bf16},
+    {K_TWALK_BF16, "conv_twalk_bf16", &Conv::dw, false, false, xg_twalk_bf16},
+    {K_PROJ_X3, "conv_proj_x3", &Conv::dx3, false, false, xg_proj_x3},
+    {K_DMA_X3, "conv_dma_x3", &Conv::dx3, false, false, xg_dma_x3},
+    {K_STEM_F32, "conv_stem_f32", &Conv::dw, true, false, xg_gemm},
+    {K_DMA_W, "conv_dma_w", &Conv::dw, false, false, xg_gemm},
+    {K_DMA, "conv_dma", &Conv::dw, false, false, xg_gemm},
+};
+constexpr bool kernels_in_order() {
+  int i = 0;
+  for (const KernelInfo& k : kKernels)
+    if (k.id != i++) return false;
+  return i == K_DMA + 1;
+}
+static_assert(kernels_in_order(), "kKernels: one row per Kernel enumerator, in the enum's order");
 
 // Conv parameters of c over an input of shape `in` (output shape in `out`; tensors unset).
 ConvParams conv_params(const Conv& c, const Shape5& in, Shape5& out) {
@@ -432,64 +691,65 @@ ConvParams conv_params(const Conv& c, const Shape5& in, Shape5& out) {
 }
 
 // The kernel run_conv launches for c with parameters p (p.vflags selects A/B variants).
-const char* pick_kernel(const Conv& c, ConvParams p) {
+Kernel pick_kernel(const Conv& c, ConvParams p) {
   // 7x7 maps (layer4 at 112x112 clips): the split-bf16 direct GEMM beats F(4x4)'s partial edge tiles
   // (convbench 0.284 vs 0.312 ms per 1152-channel launch, profiles/r03p_dma_x3_tiles.txt); per-clip
   // shape rule
-  if (c.dwino4 && c.dx3 && p.Ho * p.Wo <= 64 && !p.y_c8 && dma_x3_supported(p)) return "conv_dma_x3";
+  if (c.dwino4 && c.dx3 && p.Ho * p.Wo <= 64 && !p.y_c8 && dma_x3_supported(p)) return K_DMA_X3;
   const int no4 = p.vflags & (CLASFV_VARIANT_NO_WINO4 | CLASFV_VARIANT_NO_WINO4W);
-  if (c.dwino4r && !no4 && !(p.vflags & CLASFV_VARIANT_NO_WINO4R) && wino4r_supported(p)) return "conv_wino4r";
-  if (c.dwino4w && !no4 && wino4w_supported(p)) return "conv_wino4w";
-  if (c.dwino4 && !(p.vflags & CLASFV_VARIANT_NO_WINO4) && wino4_supported(p)) return "conv_wino4";
+  if (c.dwino4r && !no4 && !(p.vflags & CLASFV_VARIANT_NO_WINO4R) && wino4r_supported(p)) return K_WINO4R;
+  if (c.dwino4w && !no4 && wino4w_supported(p)) return K_WINO4W;
+  if (c.dwino4 && !(p.vflags & CLASFV_VARIANT_NO_WINO4) && wino4_supported(p)) return K_WINO4;
   if (c.dwino) {
     const bool no_patch = (p.vflags & CLASFV_VARIANT_NO_WINO_PATCH) != 0;
-    if (!no_patch && winoq_supported(p)) return "conv_wino_q";
-    if (wino_supported(p)) return "conv_wino";
+    if (!no_patch && winoq_supported(p)) return K_WINO_Q;
+    if (wino_supported(p)) return K_WINO;
   }
-  if (c.dws16 && !(p.vflags & CLASFV_VARIANT_NO_STEM_BF16) && stem_bf16_supported(p)) return "conv_stem_bf16";
-  if (c.dws16 && stem_x3_supported(p)) return "conv_stem_x3";
+  if (c.dws16 && !(p.vflags & CLASFV_VARIANT_NO_STEM_BF16) && stem_bf16_supported(p)) return K_STEM_BF16;
+  if (c.dws16 && stem_x3_supported(p)) return K_STEM_X3;
   // temporal convs on <= 256-voxel clip maps (layer4, T = 4): split-K 4 on the split-bf16 direct GEMM
   // beats the one-tile-row F(4,3) form (convbench 0.119 vs 0.145 ms with both split sums)
   if (c.dwinot && c.dx3 && (long)p.To * p.Ho * p.Wo <= 256 && !p.x_c8 && !p.y_c8 && dma_x3_supported(p))
-    return "conv_dma_x3";
-  if (c.dwinot && winot_supported(p)) return "conv_winot";
-  if (c.dx3 && !(p.vflags & CLASFV_VARIANT_NO_PROJ_X3) && proj_x3_supported(p)) return "conv_proj_x3";
+    return K_DMA_X3;
+  if (c.dwinot && winot_supported(p)) return K_WINOT;
+  if (c.dx3 && !(p.vflags & CLASFV_VARIANT_NO_PROJ_X3) && proj_x3_supported(p)) return K_PROJ_X3;
   if (!(p.vflags & (CLASFV_VARIANT_NO_PATCH_BF16 | CLASFV_VARIANT_NO_PATCH32)) && patch32_bf16_supported(p))
-    return "conv_patch32_bf16";
+    return K_PATCH32_BF16;
   if (!(p.vflags & (CLASFV_VARIANT_NO_PATCH_BF16 | CLASFV_VARIANT_NO_TWALK)) && twalk_bf16_supported(p))
-    return "conv_twalk_bf16";
-  if (!(p.vflags & CLASFV_VARIANT_NO_PATCH_BF16) && patch_bf16_supported(p)) return "conv_patch_bf16";
-  if (c.dx3 && dma_x3_supported(p)) return "conv_dma_x3";
-  if (c.stem) return "conv_stem_f32";
+    return K_TWALK_BF16;
+  if (!(p.vflags & CLASFV_VARIANT_NO_PATCH_BF16) && patch_bf16_supported(p)) return K_PATCH_BF16;
+  if (c.dx3 && dma_x3_supported(p)) return K_DMA_X3;
+  if (c.stem) return K_STEM_F32;
   // bf16 direct convs with whole 128-B tap rows (launch_dma takes conv_dma_w at the 128-row M tile)
-  return dma_w_ok(p) ? "conv_dma_w" : "conv_dma";
+  return dma_w_ok(p) ? K_DMA_W : K_DMA;
 }
 
 // Whether the mid tensor between producer `a` (input shape `in`) and consumer `b` goes through HBM
-// in the 8-channel-blocked layout: `a` runs on a kernel that writes it and `b` on conv_winot5,
-// which reads it (CLASFV_VARIANT_NO_C8: always channels-last).
+// in the 8-channel-blocked layout: `a` runs on a kernel that writes it and `b` on one that reads it
+// (conv_winot where launch_winot takes conv_winot5; CLASFV_VARIANT_NO_C8: always channels-last).
+// The choice depends on shapes and flags only: no *_supported test reads ConvParams::w.
 bool c8_pair(const Conv& a, const Conv& b, const Shape5& in, const Tuning& tu) {
   if (tu.vflags & CLASFV_VARIANT_NO_C8) return false;
   Shape5 mid, out;
   ConvParams pa = conv_params(a, in, mid);
   ConvParams pb = conv_params(b, mid, out);
-  pa.w = a.dwino4w ? (const void*)a.dwino4w : a.dwino4 ? (const void*)a.dwino4 : a.dwino ? (const void*)a.dwino : a.dw;
-  pb.w = b.dwinot;
   pa.vflags = pb.vflags = tu.vflags;
-  const char* ka = pick_kernel(a, pa);
-  // Measured per producer (30 clips, profiles/r02j_*): stem and conv_wino_q (layer1, layer2) write
-  // the blocked layout at no cost while the temporal kernels after them gain 7-24 %; conv_wino
-  // (layer3) broke even and stays channels-last.
-  const bool writes = !strcmp(ka, "conv_wino4") || !strcmp(ka, "conv_wino4w") || !strcmp(ka, "conv_wino4r") ||
-                      !strcmp(ka, "conv_wino_q") ||
-                      !strcmp(ka, "conv_stem_f32") ||
-                      !strcmp(ka, "conv_stem_x3");
-  return writes && !a.out_bf16 && !strcmp(pick_kernel(b, pb), "conv_winot") && winot_c8_ok(pb);
+  return kKernels[pick_kernel(a, pa)].writes_c8 && !a.out_bf16 && kKernels[pick_kernel(b, pb)].reads_c8 &&
+         winot_c8_ok(pb);
 }
 
+// Split-K into S partial sums in the caller's scratch, where S > 1 and the scratch holds them.
+void split_k(ConvParams& p, int S, void* scratch, size_t scratch_bytes) {
+  if (S > 1 && scratch && (size_t)S * p.M * p.Cout * sizeof(float) <= scratch_bytes) {
+    p.part = reinterpret_cast<float*>(scratch);
+    p.n_split = S;
+  }
+}
+
+// Runs c on the kernel pick_kernel chooses; *kernel is its kKernels row once chosen.
 int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-             hipStream_t s, const void* zero_block, const void* x2, const char** kname, const Tuning& tu, int x_c8 = 0,
-             int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0) {
+             hipStream_t s, const void* zero_block, const void* x2, const KernelInfo** kernel, const Tuning& tu,
+             int x_c8 = 0, int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0) {
   if (in.c != c.cin_p) return fail(CLASFV_EINVAL, "internal: channel mismatch");
   ConvParams p = conv_params(c, in, out);
   p.vflags = tu.vflags;
@@ -502,73 +762,44 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
   p.x2 = x2;
   p.x_c8 = x_c8;
   p.y_c8 = y_c8;
-  const char* k = pick_kernel(c, p);
-  *kname = k;
-  const bool c8_out = !strcmp(k, "conv_wino4") || !strcmp(k, "conv_wino4w") || !strcmp(k, "conv_wino4r") ||
-                      !strcmp(k, "conv_wino_q") ||
-                      !strcmp(k, "conv_stem_f32") ||
-                      !strcmp(k, "conv_stem_x3");
-  if ((y_c8 && !c8_out) || (x_c8 && strcmp(k, "conv_winot")))
+  const KernelInfo& k = kKernels[pick_kernel(c, p)];
+  *kernel = &k;
+  if ((y_c8 && !k.writes_c8) || (x_c8 && !k.reads_c8))
     return fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
-  if (!strcmp(k, "conv_wino4r")) {
-    p.w = c.dwino4r;
-    HIP_TRY(launch_wino4r(p, s));
-  } else if (!strcmp(k, "conv_wino4w")) {
-    p.w = c.dwino4w;
-    HIP_TRY(launch_wino4w(p, s));
-  } else if (!strcmp(k, "conv_wino4")) {
-    p.w = c.dwino4;
-    HIP_TRY(launch_wino4(p, s));
-  } else if (!strcmp(k, "conv_wino_q")) {
-    p.w = c.dwino;
-    HIP_TRY(launch_winoq(p, s));
-  } else if (!strcmp(k, "conv_wino")) {
-    p.w = c.dwino;
-    HIP_TRY(launch_wino(p, s));
-  } else if (!strcmp(k, "conv_stem_bf16")) {
-    p.w = c.dws16;
-    HIP_TRY(launch_stem_bf16(p, s));
-  } else if (!strcmp(k, "conv_stem_x3")) {
-    p.w = c.dws16;
-    HIP_TRY(launch_stem_x3(p, s));
-  } else if (!strcmp(k, "conv_winot")) {
-    p.w = c.dwinot;
-    // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
-    const int S = winot_split_for(p);
-    if (S > 1 && scratch && (size_t)S * p.M * p.Cout * sizeof(float) <= scratch_bytes) {
-      p.part = reinterpret_cast<float*>(scratch);
-      p.n_split = S;
-    }
-    HIP_TRY(launch_winot(p, s));
-  } else if (!strcmp(k, "conv_patch_bf16")) {
-    HIP_TRY(launch_patch_bf16(p, s));
-  } else if (!strcmp(k, "conv_patch32_bf16")) {
-    HIP_TRY(launch_patch32_bf16(p, s));
-  } else if (!strcmp(k, "conv_twalk_bf16")) {
-    HIP_TRY(launch_twalk_bf16(p, s));
-  } else if (!strcmp(k, "conv_proj_x3")) {
-    p.w = c.dx3;
-    HIP_TRY(launch_proj_x3(p, s));
-  } else if (!strcmp(k, "conv_dma_x3")) {
-    p.w = c.dx3;
-    const int S = dma_split_for(p, 2);
-    if (S > 1 && scratch && (size_t)S * p.M * p.Cout * sizeof(float) <= scratch_bytes) {
-      p.part = reinterpret_cast<float*>(scratch);
-      p.n_split = S;
-    }
-    HIP_TRY(launch_dma_x3(p, dma_x3_bn(c.cout_p), s));
-  } else {
-    int mt = 2, bn = c.cout_p;  // stem: one N tile (48 fp32 / 64 bf16 channels)
-    if (!c.stem) {
+  p.w = c.*k.image;
+  switch (k.id) {  // no default: a Kernel without a launch is a compiler warning
+    case K_WINO4R: HIP_TRY(launch_wino4r(p, s)); break;
+    case K_WINO4W: HIP_TRY(launch_wino4w(p, s)); break;
+    case K_WINO4: HIP_TRY(launch_wino4(p, s)); break;
+    case K_WINO_Q: HIP_TRY(launch_winoq(p, s)); break;
+    case K_WINO: HIP_TRY(launch_wino(p, s)); break;
+    case K_STEM_BF16: HIP_TRY(launch_stem_bf16(p, s)); break;
+    case K_STEM_X3: HIP_TRY(launch_stem_x3(p, s)); break;
+    case K_WINOT:
+      // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
+      split_k(p, winot_split_for(p), scratch, scratch_bytes);
+      HIP_TRY(launch_winot(p, s));
+      break;
+    case K_PATCH_BF16: HIP_TRY(launch_patch_bf16(p, s)); break;
+    case K_PATCH32_BF16: HIP_TRY(launch_patch32_bf16(p, s)); break;
+    case K_TWALK_BF16: HIP_TRY(launch_twalk_bf16(p, s)); break;
+    case K_PROJ_X3: HIP_TRY(launch_proj_x3(p, s)); break;
+    case K_DMA_X3:
+      split_k(p, dma_split_for(p, 2), scratch, scratch_bytes);
+      HIP_TRY(launch_dma_x3(p, dma_x3_bn(c.cout_p), s));
+      break;
+    case K_STEM_F32:  // one N tile (48 fp32 / 64 bf16 channels)
+      HIP_TRY(launch_conv(p, 2, c.cout_p, s));
+      break;
+    case K_DMA_W:
+    case K_DMA: {
+      int mt, bn;
       conv_pick_tile(p.M, c.cout_p, tu.conv_nt, &mt, &bn);
       // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
-      const int S = dma_split_for(p, mt);
-      if (S > 1 && scratch && (size_t)S * p.M * p.Cout * sizeof(float) <= scratch_bytes) {
-        p.part = reinterpret_cast<float*>(scratch);
-        p.n_split = S;
-      }
+      split_k(p, dma_split_for(p, mt), scratch, scratch_bytes);
+      HIP_TRY(launch_conv(p, mt, bn, s));
+      break;
     }
-    HIP_TRY(launch_conv(p, mt, bn, s));
   }
   return CLASFV_OK;
 }
@@ -626,6 +857,35 @@ int tick(clasfv_engine* h, hipStream_t s) {
 }
 
 float tap_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+
+// The decoder's parameters over four tap projections (tap[i] of shape tsh[i]) for an (N, T, H, W)
+// output; idx is the launch's index table (decoder_index_bytes(T, H, W) of device memory).
+DecParams decoder_params(const clasfv_engine* h, const float* const tap[4], const Shape5 tsh[4], float* seg, float* mot,
+                         int N, int T, int H, int W, void* idx) {
+  DecParams d{};
+  for (int i = 0; i < 4; ++i) {
+    d.tap[i].p = tap[i];
+    d.tap[i].T = tsh[i].t;
+    d.tap[i].H = tsh[i].h;
+    d.tap[i].W = tsh[i].w;
+    d.tap[i].st = tap_scale(tsh[i].t, T);
+    d.tap[i].sh = tap_scale(tsh[i].h, H);
+    d.tap[i].sw = tap_scale(tsh[i].w, W);
+  }
+  d.b1 = h->b1;
+  d.w2 = h->w2;
+  d.b2 = h->b2;
+  d.wh = h->wh;
+  d.bh = h->bh;
+  d.seg = seg;
+  d.mot = mot;
+  d.N = N, d.T = T, d.H = H, d.W = W;
+  d.bf16 = h->dtype == CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_BF16);
+  d.w2x3 = h->w2x3;
+  d.x3 = h->dtype != CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_X3);
+  d.idx = idx;
+  return d;
+}
 
 // Makes the handle's device current for the scope of an ABI call and restores the caller's.
 struct DeviceGuard {
@@ -719,21 +979,8 @@ int clasfv_create(int device, clasfv_t* out) {
 int clasfv_destroy(clasfv_t h) {
   if (!h) return CLASFV_OK;
   DeviceGuard guard(h->device);
-  for (auto& c : h->convs) {
-    (void)hipFree(c.dw);
-    (void)hipFree(c.db);
-    (void)hipFree(c.dwino);
-    (void)hipFree(c.dwino4);
-    (void)hipFree(c.dwino4w);
-    (void)hipFree(c.dwino4r);
-    (void)hipFree(c.dwinot);
-    (void)hipFree(c.dws16);
-    (void)hipFree(c.dx3);
-  }
-  for (auto& c : h->proj) {
-    (void)hipFree(c.dw);
-    (void)hipFree(c.dx3);
-  }
+  for (auto& c : h->convs) free_conv_images(c);
+  for (auto& c : h->proj) free_conv_images(c);
   for (auto* c : h->ctxs) {
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -795,158 +1042,10 @@ int clasfv_finalize(clasfv_t h) {
   const bool bf16 = h->dtype == CLASFV_DTYPE_BF16;
   for (auto& c : h->convs) layout_conv(c, bf16);
   for (auto& c : h->proj) layout_conv(c, bf16);
-  std::vector<double> s, t;
-  for (auto& c : h->convs) {
-    (void)hipFree(c.dw);
-    (void)hipFree(c.db);
-    (void)hipFree(c.dwino);
-    (void)hipFree(c.dwino4);
-    (void)hipFree(c.dwino4w);
-    (void)hipFree(c.dwino4r);
-    (void)hipFree(c.dwinot);
-    (void)hipFree(c.dws16);
-    (void)hipFree(c.dx3);
-    c.dw = c.dws16 = c.dx3 = nullptr;
-    c.db = nullptr;
-    c.dwino = c.dwino4 = c.dwino4w = c.dwino4r = c.dwinot = nullptr;
-    bn_scale_shift(h, c.bn, c.cout, s, t);
-    const auto& w = P(h, c.w + ".weight");
-    const int taps = c.kt * c.kh * c.kw;
-    const int cin = c.cin;
-    int rc = upload_conv(
-        c, [&](int o, int ci, int tap) { return w[((size_t)o * cin + ci) * taps + tap]; }, s, t, true);
-    if (rc) return rc;
-    if (use_wino(c, bf16, h->tune.vflags)) {
-      std::vector<double> wf((size_t)c.cout * cin * 9);
-      for (int o = 0; o < c.cout; ++o)
-        for (size_t i = 0; i < (size_t)cin * 9; ++i) wf[(size_t)o * cin * 9 + i] = (double)w[(size_t)o * cin * 9 + i] * s[o];
-      std::vector<float> u((size_t)16 * c.cin_p * c.cout_p);
-      wino_transform_weights(wf.data(), c.cout, cin, c.cout_p, c.cin_p, u.data());
-      if ((rc = upload(u, &c.dwino))) return rc;
-      if (c.cout_p % 48 == 0 && c.cin_p % 8 == 0) {
-        std::vector<float> u4(wino4_weight_floats(c.cin_p, c.cout_p));
-        wino4_transform_weights(wf.data(), c.cout, cin, c.cout_p, c.cin_p, u4.data());
-        if ((rc = upload(u4, &c.dwino4))) return rc;
-      }
-      if (c.cin_p % 8 == 0 && wino4w_weight_floats(c.cin_p, c.cout_p)) {
-        std::vector<float> uw(wino4w_weight_floats(c.cin_p, c.cout_p));
-        wino4w_transform_weights(wf.data(), c.cout, cin, c.cout_p, c.cin_p, uw.data());
-        if ((rc = upload(uw, &c.dwino4w))) return rc;
-      }
-      if (c.cin_p % 8 == 0 && wino4r_weight_floats(c.cin_p, c.cout_p)) {
-        std::vector<float> ur(wino4r_weight_floats(c.cin_p, c.cout_p));
-        wino4r_transform_weights(wf.data(), c.cout, cin, c.cout_p, c.cin_p, ur.data());
-        if ((rc = upload(ur, &c.dwino4r))) return rc;
-      }
-    }
-    if (!bf16 && c.stem && c.cout_p == 48 && c.kh == 7 && c.kw == 7 && cin <= 4) {  // conv_stem_x3's pieces
-      const size_t img = (size_t)48 * 7 * 8 * 4;
-      std::vector<float> ws(3 * img, 0.f);  // hi, mid, lo: bf16 of the remainder, in double
-      for (int o = 0; o < c.cout; ++o)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int kh = 0; kh < 7; ++kh)
-            for (int kw = 0; kw < 7; ++kw) {
-              double r = (double)(float)((double)w[((size_t)o * cin + ci) * 49 + kh * 7 + kw] * s[o]);
-              const size_t k = (((size_t)o * 7 + kh) * 8 + kw) * 4 + ci;
-              for (int pc = 0; pc < 3; ++pc) {
-                const uint32_t hb = (uint32_t)to_bf16((float)r) << 16;
-                float f;
-                memcpy(&f, &hb, 4);
-                ws[pc * img + k] = f;
-                r -= f;
-              }
-            }
-      if ((rc = upload_bf16(ws, &c.dws16))) return rc;
-    }
-    if (bf16 && c.stem && c.cout_p == 64 && c.kh == 7 && c.kw == 7 && cin <= 4) {  // conv_stem_bf16's K order
-      const size_t img = (size_t)64 * 7 * 8 * 4;
-      std::vector<float> ws(2 * img, 0.f);  // hi image, then lo = bf16(w - hi)
-      for (int o = 0; o < c.cout; ++o)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int kh = 0; kh < 7; ++kh)
-            for (int kw = 0; kw < 7; ++kw) {
-              const float v = (float)((double)w[((size_t)o * cin + ci) * 49 + kh * 7 + kw] * s[o]);
-              const uint32_t hb = (uint32_t)to_bf16(v) << 16;
-              float hi;
-              memcpy(&hi, &hb, 4);
-              const size_t k = (((size_t)o * 7 + kh) * 8 + kw) * 4 + ci;
-              ws[k] = hi;
-              ws[img + k] = v - hi;
-            }
-      if ((rc = upload_bf16(ws, &c.dws16))) return rc;
-    }
-    if (use_winot(c, bf16, h->tune.vflags)) {
-      std::vector<double> wf((size_t)c.cout * cin * 3);
-      for (int o = 0; o < c.cout; ++o)
-        for (size_t i = 0; i < (size_t)cin * 3; ++i) wf[(size_t)o * cin * 3 + i] = (double)w[(size_t)o * cin * 3 + i] * s[o];
-      std::vector<float> u((size_t)6 * c.cin_p * c.cout_p);
-      winot_transform_weights(wf.data(), c.cout, cin, c.cout_p, c.cin_p, u.data());
-      if ((rc = upload(u, &c.dwinot))) return rc;
-    }
-  }
-  // comb_1 + BN1 folded, split per tap (concat order stem, layer1, layer2, layer3, layer4)
-  bn_scale_shift(h, "comb_batch_norm_1", 64, s, t);
-  const auto& w1 = P(h, "comb_1_layer.weight");
-  const auto& bias1 = P(h, "comb_1_layer.bias");
-  std::vector<double> zero(64, 0.0);
-  const int col0[5] = {0, 64, 128, 256, 512};
-  for (int i = 0; i < 5; ++i) {
-    if (i == 1) continue;  // folded into the dual proj[0]
-    Conv& c = h->proj[i];
-    (void)hipFree(c.dw);
-    (void)hipFree(c.dx3);
-    c.dw = c.dx3 = nullptr;
-    const int o0 = col0[i];
-    const int kin = c.cin + c.cin2;
-    Conv tmp = c;  // upload_conv walks cin: give it the concatenated width
-    tmp.cin = tmp.cin_p = kin;
-    int rc = upload_conv(
-        tmp, [&](int o, int ci, int) { return w1[(size_t)o * 1024 + o0 + ci]; }, s, zero, false);
-    if (rc) return rc;
-    c.dw = tmp.dw;
-    c.dx3 = tmp.dx3;
-  }
-  std::vector<float> b1(64);
-  for (int o = 0; o < 64; ++o) b1[o] = (float)(s[o] * (double)bias1[o] + t[o]);
-  bn_scale_shift(h, "comb_batch_norm_2", 64, s, t);
-  const auto& w2 = P(h, "comb_2_layer.weight");
-  const auto& bias2 = P(h, "comb_2_layer.bias");
-  std::vector<float> w2f(64 * 64), b2(64);
-  for (int o = 0; o < 64; ++o) {
-    for (int k = 0; k < 64; ++k) w2f[o * 64 + k] = (float)((double)w2[o * 64 + k] * s[o]);
-    b2[o] = (float)(s[o] * (double)bias2[o] + t[o]);
-  }
-  const auto& ws = P(h, "segmentation_head.weight");
-  const auto& bs = P(h, "segmentation_head.bias");
-  const auto& wm = P(h, "motion_head.weight");
-  const auto& bm = P(h, "motion_head.bias");
-  std::vector<float> whf(8 * 64, 0.f), bhf(8, 0.f);
-  for (int k = 0; k < 64; ++k) {
-    whf[0 * 64 + k] = ws[k];
-    whf[1 * 64 + k] = ws[64 + k];
-    for (int m = 0; m < 4; ++m) whf[(2 + m) * 64 + k] = wm[m * 64 + k];
-  }
-  bhf[0] = bs[0];
-  bhf[1] = bs[1];
-  for (int m = 0; m < 4; ++m) bhf[2 + m] = bm[m];
-  for (float** d : {&h->b1, &h->w2, &h->b2, &h->wh, &h->bh}) {
-    (void)hipFree(*d);
-    *d = nullptr;
-  }
-  // W2 and the head weights as hi + mid + lo bf16 pieces in the X3 decoder's lane order
-  std::vector<uint16_t> w2x3(DECODER_X3_ELEMS);
-  decoder_x3_weights(w2f.data(), whf.data(), w2x3.data());
-  (void)hipFree(h->w2x3);
-  h->w2x3 = nullptr;
-  int rc = upload(b1, &h->b1);
-  if (!rc) rc = upload(w2f, &h->w2);
-  if (!rc && hipMalloc(&h->w2x3, w2x3.size() * sizeof(uint16_t)) != hipSuccess) rc = fail(CLASFV_EHIP, "hipMalloc");
-  if (!rc && hipMemcpy(h->w2x3, w2x3.data(), w2x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(CLASFV_EHIP, "hipMemcpy");
-  if (!rc) rc = upload(b2, &h->b2);
-  if (!rc) rc = upload(whf, &h->wh);
-  if (!rc) rc = upload(bhf, &h->bh);
-  if (rc) return rc;
+  for (auto& c : h->convs)
+    if (int rc = finalize_conv(h, c, bf16)) return rc;
+  if (int rc = finalize_projections(h)) return rc;
+  if (int rc = finalize_decoder(h)) return rc;
   if (!h->zero) {
     HIP_TRY(hipMalloc(&h->zero, 256));
     HIP_TRY(hipMemset(h->zero, 0, 256));
@@ -1037,17 +1136,17 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     HIP_TRY(hipStreamWaitEvent(cx->side, cx->ev_fork, 0));
     side_join.pending = true;
     const int e0 = h->ktime ? tick(h, cx->side) : -1;
-    const char* kname = "";
-    int rc_ = run_conv(c, xin, in, y, out, nullptr, false, cx->side, h->zero, x2, &kname, h->tune);
+    const KernelInfo* k = nullptr;
+    int rc_ = run_conv(c, xin, in, y, out, nullptr, false, cx->side, h->zero, x2, &k, h->tune);
     if (!rc_ && e0 >= 0) {
       const int e1 = tick(h, cx->side);
-      if (e1 >= 0) h->recs.push_back({kname, conv_gflop(c, out), conv_exec_gflop(c, out, kname), e0, e1});
+      if (e1 >= 0) h->recs.push_back({k->name, conv_gflop(c, out), k->xgflop(c, out), e0, e1});
     }
     return rc_;
   };
   auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
                  const void* x2 = nullptr, int x_c8 = 0, int y_c8 = 0) {
-    const char* kname = "";
+    const KernelInfo* k = nullptr;
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
     if (xin == buf(MID)) {
@@ -1057,9 +1156,8 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
         scratch_bytes = mid_bytes - used;
       }
     }
-    int rc_ = run_conv(c, xin, in, y, out, res, relu, s, h->zero, x2, &kname, h->tune, x_c8, y_c8, scratch,
-                       scratch_bytes);
-    if (!rc_) timed(kname, conv_gflop(c, out), conv_exec_gflop(c, out, kname));
+    int rc_ = run_conv(c, xin, in, y, out, res, relu, s, h->zero, x2, &k, h->tune, x_c8, y_c8, scratch, scratch_bytes);
+    if (!rc_) timed(k->name, conv_gflop(c, out), k->xgflop(c, out));
     return rc_;
   };
 
@@ -1117,30 +1215,11 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   if ((rc = run(h->proj[4], taps[4], taps_shape[4], buf(PP4), sp4, nullptr, false))) return rc;
   HIP_TRY(side_join.join());  // the side stream's projections are complete before the decoder
 
-  DecParams d{};
   const Shape5 tsh[4] = {sp, sp2, sp3, sp4};
   const int tb[4] = {P01, PP2, PP3, PP4};
-  for (int i = 0; i < 4; ++i) {
-    d.tap[i].p = reinterpret_cast<const float*>(buf(tb[i]));
-    d.tap[i].T = tsh[i].t;
-    d.tap[i].H = tsh[i].h;
-    d.tap[i].W = tsh[i].w;
-    d.tap[i].st = tap_scale(tsh[i].t, T);
-    d.tap[i].sh = tap_scale(tsh[i].h, H);
-    d.tap[i].sw = tap_scale(tsh[i].w, W);
-  }
-  d.b1 = h->b1;
-  d.w2 = h->w2;
-  d.b2 = h->b2;
-  d.wh = h->wh;
-  d.bh = h->bh;
-  d.seg = seg;
-  d.mot = mot;
-  d.N = N, d.T = T, d.H = H, d.W = W;
-  d.bf16 = h->dtype == CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_BF16);
-  d.w2x3 = h->w2x3;
-  d.x3 = h->dtype != CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_X3);
-  d.idx = buf(DIDX);
+  const float* tp[4];
+  for (int i = 0; i < 4; ++i) tp[i] = reinterpret_cast<const float*>(buf(tb[i]));
+  const DecParams d = decoder_params(h, tp, tsh, seg, mot, N, T, H, W, buf(DIDX));
   HIP_TRY(launch_decoder(d, s));
   // comb_2 (64x64) and the heads (6 useful of the 16 rows of their MFMA tile) per output voxel, in the
   // products of the pipe they run on: fp32 engines six split-bf16 products each (bf16 pipe), bf16
@@ -1228,10 +1307,10 @@ int clasfv_run_conv(clasfv_t h, int i, const void* x, int N, int T, int H, int W
   DEVICE_GUARD(h->device);
   const Shape5 in{N, T, H, W, c->cin_p};
   Shape5 out;
-  const char* kname = "";
-  int rc = run_conv(*c, x, in, y, out, res, relu != 0, (hipStream_t)stream, h->zero, x2, &kname, h->tune, x_c8, y_c8,
+  const KernelInfo* k = nullptr;
+  int rc = run_conv(*c, x, in, y, out, res, relu != 0, (hipStream_t)stream, h->zero, x2, &k, h->tune, x_c8, y_c8,
                     scratch_bytes ? scratch : nullptr, (size_t)scratch_bytes);
-  if (kernel_name) *kernel_name = kname;
+  if (kernel_name) *kernel_name = k ? k->name : "";
   return rc;
 }
 
@@ -1254,29 +1333,13 @@ int clasfv_run_decoder(clasfv_t h, const float* p01, const float* p2, const floa
   // (3-wide kernels, stride 2, padding 1: d -> (d - 1) / 2 + 1)
   auto half = [](int d) { return (d - 1) / 2 + 1; };
   const float* taps[4] = {p01, p2, p3, p4};
-  DecParams d{};
+  Shape5 tsh[4];
   int t = T, hh = half(H), ww = half(W);
   for (int k = 0; k < 4; ++k) {
     if (k) t = half(t), hh = half(hh), ww = half(ww);
-    d.tap[k].p = taps[k];
-    d.tap[k].T = t, d.tap[k].H = hh, d.tap[k].W = ww;
-    d.tap[k].st = tap_scale(t, T);
-    d.tap[k].sh = tap_scale(hh, H);
-    d.tap[k].sw = tap_scale(ww, W);
+    tsh[k] = Shape5{N, t, hh, ww, 64};
   }
-  d.b1 = h->b1;
-  d.w2 = h->w2;
-  d.b2 = h->b2;
-  d.wh = h->wh;
-  d.bh = h->bh;
-  d.seg = seg;
-  d.mot = mot;
-  d.N = N, d.T = T, d.H = H, d.W = W;
-  d.bf16 = h->dtype == CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_BF16);
-  d.w2x3 = h->w2x3;
-  d.x3 = h->dtype != CLASFV_DTYPE_BF16 && !(h->tune.vflags & CLASFV_VARIANT_NO_DECODER_X3);
-  d.idx = cx->arena + L.off[DIDX];
-  HIP_TRY(launch_decoder(d, s));
+  HIP_TRY(launch_decoder(decoder_params(h, taps, tsh, seg, mot, N, T, H, W, cx->arena + L.off[DIDX]), s));
   return CLASFV_OK;
 }
 

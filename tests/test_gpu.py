@@ -1600,3 +1600,67 @@ def test_cli_config0_single_clip_non_strict_vs_cpu(tmp_path):
     ref = fuse_ref.pass_labels(video, cpu_model, 0, True, to_numpy=lambda t: t.numpy())
     assert got.dtype == np.int64 and got.shape == ref.shape == (32, 112, 112)
     assert dice_delta(got, ref) <= DICE_TOL
+
+
+# (environment variable, value that switches it on, variant name): the 22 switches of include/clasfv.h
+VARIANT_ENV = [("CLASFV_WINOGRAD", "0", "no_winograd"), ("CLASFV_NO_WINO_PATCH", "1", "no_wino_patch"),
+               ("CLASFV_WINOT_REFERENCE", "1", "winot_reference"), ("CLASFV_NO_C8", "1", "no_c8"),
+               ("CLASFV_NO_STEM_BF16", "1", "no_stem_bf16"), ("CLASFV_NO_PATCH_BF16", "1", "no_patch_bf16"),
+               ("CLASFV_NO_DECODER_BF16", "1", "no_decoder_bf16"), ("CLASFV_WINOT_TS1", "0", "winot_no_ts1"),
+               ("CLASFV_NO_SPLIT_K", "1", "no_split_k"), ("CLASFV_NO_WINO4", "1", "no_wino4"),
+               ("CLASFV_NO_DECODER_X3", "1", "no_decoder_x3"), ("CLASFV_NO_DMA_X3", "1", "no_dma_x3"),
+               ("CLASFV_NO_STEM_X3", "1", "no_stem_x3"), ("CLASFV_NO_WINO4W", "1", "no_wino4w"),
+               ("CLASFV_NO_PATCH32", "1", "no_patch32"), ("CLASFV_NO_PROJ_X3", "1", "no_proj_x3"),
+               ("CLASFV_NO_WINO4R", "1", "no_wino4r"), ("CLASFV_NO_DMA_BUF", "1", "no_dma_buf"),
+               ("CLASFV_W4R_CACHED_STORES", "1", "w4r_cached_stores"),
+               ("CLASFV_PATCH32_CACHED_STORES", "", "patch32_cached_stores"),  # set to anything, empty included
+               ("CLASFV_NO_DMA_W", "0", "no_dma_w"), ("CLASFV_NO_TWALK", "yes", "no_twalk")]
+RETIRED_VARIANT_BITS = (131072, 1048576, 2097152, 8388608, 33554432)
+
+
+def test_variant_switches_from_environment_and_set_reject():
+    """The engine's one table of kernel-variant switches, from both ends. clasfv_create reads each
+    switch from its own environment variable (two are the "=0" form) and sets exactly its bit;
+    clasfv_set_kernel_variants takes every bit of _lib.VARIANTS and rejects the retired bits and
+    the first unassigned one, leaving the flags as they were. No weights are loaded."""
+    from clasfv_amd import _lib
+    from clasfv_amd.model import Engine
+    assert len(VARIANT_ENV) == 22 and {v for _, _, v in VARIANT_ENV} == set(_lib.VARIANTS)
+
+    def flags_at_create():
+        eng = Engine()
+        return eng.lib.clasfv_get_kernel_variants(eng.h)
+
+    found = {n: os.environ.pop(n) for n, _, _ in VARIANT_ENV if n in os.environ}
+    try:
+        assert flags_at_create() == 0
+        for name, value, variant in VARIANT_ENV:
+            os.environ[name] = value
+            try:
+                assert flags_at_create() == _lib.VARIANTS[variant], name
+            finally:
+                del os.environ[name]
+        os.environ["CLASFV_WINOGRAD"] = os.environ["CLASFV_WINOT_TS1"] = "1"
+        try:
+            assert flags_at_create() == 0
+        finally:
+            del os.environ["CLASFV_WINOGRAD"], os.environ["CLASFV_WINOT_TS1"]
+    finally:
+        os.environ.update(found)
+
+    eng = Engine()
+    get = lambda: eng.lib.clasfv_get_kernel_variants(eng.h)
+    for variant, bit in _lib.VARIANTS.items():
+        eng.set_variants(variant)
+        assert get() == bit
+    eng.set_variants(*_lib.VARIANTS)
+    every = get()
+    assert every == sum(_lib.VARIANTS.values())
+    for keep in (every, _lib.VARIANTS["no_c8"], 0):
+        assert eng.lib.clasfv_set_kernel_variants(eng.h, keep) == 0
+        for bad in RETIRED_VARIANT_BITS + (1 << 27,):
+            assert not bad & every
+            for flags in (bad, bad | keep):
+                assert eng.lib.clasfv_set_kernel_variants(eng.h, flags) != 0
+                assert b"unknown kernel-variant bit" in eng.lib.clasfv_last_error()
+                assert get() == keep

@@ -499,11 +499,14 @@ def _f32_baseline(nt, c, b, x32):
 
 def test_cases_reach_every_kernel_pick_kernel_can_return():
     """Every case asserts the name clasfv_run_conv returns, so the table's expectations are the names
-    reached: together they must be every string pick_kernel returns, for each engine dtype."""
+    reached: together they must be every kernel pick_kernel returns, for each engine dtype. pick_kernel
+    returns enumerators; the kernel table (kKernels) gives each one's reported name."""
     src = open(os.path.join(REPO, "fully-automated-multi-heartbeat-echocardiography-video-segmentation-and-motion-"
                                   "tracking_amd", "csrc", "engine.hip")).read()
-    body = src[src.index("const char* pick_kernel("):src.index("bool c8_pair(")]
-    names = set(re.findall(r'"(conv_\w+)"', body))
+    table = dict(re.findall(r'\{(K_\w+), "(conv_\w+)"', src))
+    assert len(set(table.values())) == len(table) and len(re.findall(r'"conv_\w+"', src)) == len(table)
+    body = src[src.index("Kernel pick_kernel("):src.index("bool c8_pair(")]
+    names = {table[k] for k in re.findall(r"\bK_\w+", body)}
     assert names == FP32_KERNELS | BF16_KERNELS
     assert {c["kernel"] for c in CASES if c["dtype"] == "fp32"} == FP32_KERNELS
     assert {c["kernel"] for c in CASES if c["dtype"] == "bf16"} == BF16_KERNELS
