@@ -38,6 +38,39 @@ inline FastDiv fast_div(unsigned d) {
 }
 __device__ inline int fdiv(int n, FastDiv f) { return (int)((__umulhi((unsigned)n, f.m) + (unsigned)n) >> f.l); }
 
+// Launch log (clasfv_set_launch_log / clasfv_launch_log): every kernel launch the engine can reach goes
+// through CLASFV_LAUNCH, which notes the kernel function launched, its grid and its pass count in a small
+// thread-local ring before it launches; the engine empties the ring before a launcher and reads it after.
+// The label the log reports is the name under which the compiler registered that very function (template
+// arguments included; hipKernelNameRefByPtr, demangled), so nobody types it and it cannot drift from what
+// is launched -- a kernel picked at run time (a function pointer) notes itself the same way. passes: the
+// largest number of work items one wave or block processes in turn (1 unless the launcher caps its
+// grid). The cost with the log off is these stores.
+struct LaunchNote {
+  const void* kernel;  // the host-side kernel function
+  long grid;           // blocks
+  int passes;
+};
+struct LaunchRing {
+  unsigned n;
+  LaunchNote e[4];  // a launcher launches at most two kernels (the conv and its split-K sum; the decoder
+                    // and its index table)
+};
+inline thread_local LaunchRing g_launch_ring;
+inline void note_launch(const void* kernel, dim3 grid, long passes) {
+  LaunchRing& r = g_launch_ring;
+  r.e[r.n++ & 3] = LaunchNote{kernel, (long)grid.x * grid.y * grid.z, passes > 1 ? (int)passes : 1};
+}
+// CLASFV_LAUNCH_P(passes, kernel, grid, block, lds, stream, args...): hipLaunchKernelGGL with the note;
+// CLASFV_LAUNCH: passes = 1
+#define CLASFV_LAUNCH_P(passes, kernel, grid, ...)                       \
+  do {                                                                   \
+    const dim3 launch_grid_ = (grid);                                    \
+    note_launch((const void*)(kernel), launch_grid_, (passes));          \
+    hipLaunchKernelGGL(kernel, launch_grid_, __VA_ARGS__);               \
+  } while (0)
+#define CLASFV_LAUNCH(kernel, grid, ...) CLASFV_LAUNCH_P(1, kernel, grid, __VA_ARGS__)
+
 // One bias-free conv3d (BN folded into weights/bias) as an implicit GEMM over channels-last
 // activations: Y[m][n] = sum_k A[m][k] * W[n][k] (+bias[n], +res[m][n], relu).
 //   m = ((n*To + to)*Ho + ho)*Wo + wo            (output voxel)

@@ -1265,7 +1265,7 @@ hipError_t launch_dma_w(const ConvParams& p, hipStream_t s) {
   constexpr int BM = 64 * MT, BN = 16 * NT;
   const int mt = (p.M + BM - 1) / BM, nt = (p.Cout + BN - 1) / BN;
   const DmaDivs dv{fast_div(p.Wo), fast_div(p.Ho), fast_div(p.To), fast_div(nt)};
-  hipLaunchKernelGGL((conv_dma_w<MT, NT, S>), dim3(mt * nt), dim3(256), 0, s, p, nt, dv);
+  CLASFV_LAUNCH((conv_dma_w<MT, NT, S>), dim3(mt * nt), dim3(256), 0, s, p, nt, dv);
   return hipGetLastError();
 }
 
@@ -1278,9 +1278,9 @@ hipError_t launch_dma(const ConvParams& p, hipStream_t s) {
   if constexpr (sizeof(T) == 2 && MT == 2)
     if (dma_w_ok_(p)) return launch_dma_w<MT, NT, 2>(p, s);
   if (dma_buf_ok(p, sizeof(T)))
-    hipLaunchKernelGGL((conv_dma<T, MT, NT, S, true>), dim3(mt * nt * n_split), dim3(256), 0, s, p, nt, dv);
+    CLASFV_LAUNCH((conv_dma<T, MT, NT, S, true>), dim3(mt * nt * n_split), dim3(256), 0, s, p, nt, dv);
   else
-    hipLaunchKernelGGL((conv_dma<T, MT, NT, S>), dim3(mt * nt * n_split), dim3(256), 0, s, p, nt, dv);
+    CLASFV_LAUNCH((conv_dma<T, MT, NT, S>), dim3(mt * nt * n_split), dim3(256), 0, s, p, nt, dv);
   if (n_split > 1) return launch_split_sum(p, s);
   return hipGetLastError();
 }
@@ -1313,20 +1313,20 @@ hipError_t launch_dma_x3_t(const ConvParams& p, hipStream_t s) {
   // profiles/r05aq_dma_x3_wide_rows.txt -- the split-bf16 loop is not gather-bound enough for
   // whole-line rows to pay for the doubled per-lane row state)
   switch (dma_x3_buf_ok(p, nt * BN) ? ef + 8 : ef) {
-    case 0: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 0>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 1: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 1>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 2: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 2>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 3: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 3>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 8: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 0, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 9: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 1, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 10: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 2, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
-    case 11: hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, 3, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 0: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 0>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 1: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 1>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 2: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 2>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 3: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 3>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 8: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 0, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 9: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 1, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 10: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 2, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
+    case 11: CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, 3, 0, true>), grid, dim3(256), 0, s, p, nt, dv); break;
     default:
       if (ef >= 8 || ef < 4) return hipErrorInvalidValue;
       if (dma_x3_buf_ok(p, nt * BN))
-        hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN, -1, 0, true>), grid, dim3(256), 0, s, p, nt, dv);
+        CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN, -1, 0, true>), grid, dim3(256), 0, s, p, nt, dv);
       else
-        hipLaunchKernelGGL((conv_dma_x3<MT, NT, S, WN>), grid, dim3(256), 0, s, p, nt, dv);
+        CLASFV_LAUNCH((conv_dma_x3<MT, NT, S, WN>), grid, dim3(256), 0, s, p, nt, dv);
       break;
   }
   if (n_split > 1) return launch_split_sum(p, s);
@@ -1337,7 +1337,7 @@ template <int NT>
 hipError_t launch_stem(const ConvParams& p, hipStream_t s) {
   if (p.Cin != 4 || p.KT != 1 || p.KH != 7 || p.KW != 7) return hipErrorInvalidValue;  // conv_stem_f32's geometry
   const int mt = (p.M + 127) / 128, nt = (p.Cout + 16 * NT - 1) / (16 * NT);
-  hipLaunchKernelGGL((conv_stem_f32<NT>), dim3(mt * nt), dim3(256), 0, s, p, nt);
+  CLASFV_LAUNCH((conv_stem_f32<NT>), dim3(mt * nt), dim3(256), 0, s, p, nt);
   return hipGetLastError();
 }
 
@@ -1349,7 +1349,7 @@ hipError_t dma_ko_t(const ConvParams& p, hipStream_t s) {
   constexpr int BM = 128, BN = 16 * NT;
   const int mt = (p.M + BM - 1) / BM, nt = (p.Cout + BN - 1) / BN;
   const DmaDivs dv{fast_div(p.Wo), fast_div(p.Ho), fast_div(p.To), fast_div(nt)};
-  hipLaunchKernelGGL((conv_dma<__bf16, 2, NT, 3, (KO & 1) == 0, KO & ~1>), dim3(mt * nt), dim3(256), 0, s, p, nt, dv);
+  CLASFV_LAUNCH((conv_dma<__bf16, 2, NT, 3, (KO & 1) == 0, KO & ~1>), dim3(mt * nt), dim3(256), 0, s, p, nt, dv);
   return hipGetLastError();
 }
 template <int NT>
@@ -1533,7 +1533,8 @@ hipError_t launch_proj_x3(const ConvParams& p, hipStream_t s) {
   int blocks = 256;
   if (blocks * 4 > n_items) blocks = (n_items + 3) / 4;
   (void)kb;
-  hipLaunchKernelGGL((conv_proj_x3<4, 3>), dim3(blocks), dim3(256), 0, s, p, n_items);
+  const int passes = (n_items + 4 * blocks - 1) / (4 * blocks);  // 32-row items per wave (4 * blocks waves)
+  CLASFV_LAUNCH_P(passes, (conv_proj_x3<4, 3>), dim3(blocks), dim3(256), 0, s, p, n_items);
   return hipGetLastError();
 }
 
@@ -1599,7 +1600,7 @@ template <int NT, int KO>
 static hipError_t dma_x3_ko_t(const ConvParams& p, hipStream_t s) {
   const int mt = (p.M + 127) / 128, nt = (p.Cout + 16 * NT - 1) / (16 * NT);
   const DmaDivs dv{fast_div(p.Wo), fast_div(p.Ho), fast_div(p.To), fast_div(nt)};
-  hipLaunchKernelGGL((conv_dma_x3<2, NT, 2, 1, 2, (KO & 31), (KO & 32) != 0>), dim3(mt * nt), dim3(256), 0, s, p, nt, dv);
+  CLASFV_LAUNCH((conv_dma_x3<2, NT, 2, 1, 2, (KO & 31), (KO & 32) != 0>), dim3(mt * nt), dim3(256), 0, s, p, nt, dv);
   return hipGetLastError();
 }
 // conv_dma_x3 knock-outs (KO bits of conv_dma_x3; + 32: the BUF form) at MT 2, 2 stages, the ReLU
@@ -1699,8 +1700,8 @@ __global__ __launch_bounds__(256) void split_sum_kernel(const float* __restrict_
 hipError_t launch_split_sum(const ConvParams& p, hipStream_t s) {
   if (p.in_bf16 || p.out_bf16 || p.y_c8 || p.Cout % 4 || !p.part) return hipErrorInvalidValue;
   const long n4 = (long)p.M * p.Cout / 4;
-  hipLaunchKernelGGL(split_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.part, p.n_split, n4,
-                     p.Cout / 4, p.bias, (const float*)p.res, p.relu, (float*)p.y);
+  CLASFV_LAUNCH(split_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.part, p.n_split, n4,
+                p.Cout / 4, p.bias, (const float*)p.res, p.relu, (float*)p.y);
   return hipGetLastError();
 }
 
@@ -1743,7 +1744,9 @@ hipError_t launch_pack_input(const float* x, float* y, int N, int T, int HW, hip
   const size_t total = (size_t)N * T * HW;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_input_kernel, dim3(blocks), dim3(256), 0, s, x, y, N, T, HW);
+  const size_t lanes = (size_t)blocks * 256;  // the grid-stride loop's stride
+  const long passes = (long)((total + lanes - 1) / lanes);
+  CLASFV_LAUNCH_P(passes, pack_input_kernel, dim3(blocks), dim3(256), 0, s, x, y, N, T, HW);
   return hipGetLastError();
 }
 
@@ -1765,7 +1768,8 @@ hipError_t launch_stem_x3(const ConvParams& p, hipStream_t s) {
   // two blocks per CU (64.5 KiB of weight images each), or one item per block on small maps
   const int n_items = (int)((p.M + 255) / 256);
   const int grid = n_items >= 1024 ? 512 : (n_items + 7) / 8 * 8;
-  hipLaunchKernelGGL(conv_stem_x3, dim3(grid), dim3(256), 0, s, p, n_items);
+  const int passes = (n_items + grid - 1) / grid;  // items per block
+  CLASFV_LAUNCH_P(passes, conv_stem_x3, dim3(grid), dim3(256), 0, s, p, n_items);
   return hipGetLastError();
 }
 
@@ -1774,7 +1778,8 @@ hipError_t launch_stem_bf16(const ConvParams& p, hipStream_t s) {
   if (!stem_bf16_supported(p)) return hipErrorInvalidValue;
   const int n_items = (int)((p.M + 255) / 256);
   const int grid = n_items >= 1024 ? 512 : (n_items + 7) / 8 * 8;
-  hipLaunchKernelGGL(conv_stem_bf16, dim3(grid), dim3(256), 0, s, p, n_items);
+  const int passes = (n_items + grid - 1) / grid;  // items per block
+  CLASFV_LAUNCH_P(passes, conv_stem_bf16, dim3(grid), dim3(256), 0, s, p, n_items);
   return hipGetLastError();
 }
 

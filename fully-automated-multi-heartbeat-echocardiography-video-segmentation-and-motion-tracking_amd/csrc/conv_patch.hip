@@ -389,8 +389,8 @@ template <int NT, int KT, int FR, int S, bool STG, int EF>
 hipError_t launch_pe(const ConvParams& p, hipStream_t s) {
   const PatchGrid g = patch_grid(p, FR);
   const int n_tiles = p.Cout / (16 * NT);
-  hipLaunchKernelGGL((conv_patch_bf16<NT, KT, FR, S, patch_occ<NT, KT, FR, S>(), STG, EF>), dim3((unsigned)(g.base * n_tiles)),
-                     dim3(256), 0, s, p, n_tiles, g.ptw, g.npt, g.tt);
+  CLASFV_LAUNCH((conv_patch_bf16<NT, KT, FR, S, patch_occ<NT, KT, FR, S>(), STG, EF>),
+                dim3((unsigned)(g.base * n_tiles)), dim3(256), 0, s, p, n_tiles, g.ptw, g.npt, g.tt);
   return hipGetLastError();
 }
 
@@ -748,8 +748,8 @@ template <int NB, int S, int MODE>
 hipError_t launch_p32_m(const ConvParams& p, hipStream_t s) {
   const PatchGrid g = patch_grid(p, 4);
   const int n_tiles = p.Cout / (32 * NB);
-  hipLaunchKernelGGL((conv_patch32_bf16<NB, S, patch32_occ<NB, S>(), MODE>), dim3((unsigned)(g.base * n_tiles)), dim3(256),
-                     0, s, p, n_tiles, g.ptw, g.npt, g.tt);
+  CLASFV_LAUNCH((conv_patch32_bf16<NB, S, patch32_occ<NB, S>(), MODE>), dim3((unsigned)(g.base * n_tiles)), dim3(256),
+                0, s, p, n_tiles, g.ptw, g.npt, g.tt);
   return hipGetLastError();
 }
 
@@ -1126,8 +1126,8 @@ template <int NT, int FR, int S, int EF>
 hipError_t launch_s2_e(const ConvParams& p, hipStream_t s) {
   const S2Grid g = s2_grid(p, FR);
   const int n_tiles = p.Cout / (16 * NT);
-  hipLaunchKernelGGL((conv_patch_s2_bf16<NT, FR, S, s2_occ<NT, FR, S>(), EF>), dim3((unsigned)(g.base * n_tiles)),
-                     dim3(256), 0, s, p, n_tiles, g.ptw, g.npt, g.tt);
+  CLASFV_LAUNCH((conv_patch_s2_bf16<NT, FR, S, s2_occ<NT, FR, S>(), EF>), dim3((unsigned)(g.base * n_tiles)),
+                dim3(256), 0, s, p, n_tiles, g.ptw, g.npt, g.tt);
   return hipGetLastError();
 }
 

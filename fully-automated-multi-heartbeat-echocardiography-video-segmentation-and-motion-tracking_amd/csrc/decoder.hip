@@ -657,9 +657,9 @@ static hipError_t launch_dec(const DecParams& p, hipStream_t s, int mode, int th
   if (!(mode & 16)) {  // the source-index table this launch reads, filled on the same stream first
     if (!p.idx) return hipErrorInvalidValue;
     const int ne = 4 * (p.T + p.H + p.W);
-    hipLaunchKernelGGL(decoder_index_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, p);
+    CLASFV_LAUNCH(decoder_index_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, p);
   }
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(32 * th), lds, s, p);
+  CLASFV_LAUNCH(k, dim3((unsigned)nb), dim3(32 * th), lds, s, p);
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 // names (optionally "module."-prefixed, motion_segment.py:69-72); clasfv_finalize folds every
 // eval-mode BatchNorm into the preceding convolution, pads channel counts for the kernels
 // (45->48, 230->240, 460->480, 921->960) and uploads everything to HBM once.
+#include <cxxabi.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -247,6 +248,16 @@ struct clasfv_engine {
     int e0, e1;
   };
   std::vector<Rec> recs;
+  // launch log (clasfv_set_launch_log): what CLASFV_LAUNCH noted for every launch of clasfv_forward,
+  // clasfv_run_conv and clasfv_run_decoder since the last clasfv_launch_log
+  bool llog = false;
+  struct LogRec {
+    const char* label;  // into `labels`
+    long grid;
+    int passes, conv;  // conv: the diagnostics' conv index, -1 for pack_input and the decoder
+  };
+  std::vector<LogRec> log;
+  std::unordered_map<const void*, std::string> labels;  // kernel function -> instantiation label (label_of)
 };
 
 namespace {
@@ -950,6 +961,59 @@ const Conv* probe_conv(const clasfv_engine* h, int i, int* tap) {
   return i < nb ? &h->convs[i] : &h->proj[kTap[i - nb]];
 }
 
+// The diagnostics' index of a conv of h (probe_conv's numbering).
+int conv_index(const clasfv_engine* h, const Conv& c) {
+  const int nb = (int)h->convs.size();
+  if (&c >= h->convs.data() && &c < h->convs.data() + nb) return (int)(&c - h->convs.data());
+  const int i = (int)(&c - h->proj);
+  return nb + (i == 0 ? 0 : i - 1);
+}
+
+// The instantiation label of a kernel function: the name the compiler registered it under with the HIP
+// runtime, demangled, without the anonymous namespace, the return type and the parameter list:
+// "_ZN12_GLOBAL__N_111conv_winot5ILi4ELi4ELi2EEEv10ConvParamsiii7FastDiv" -> "conv_winot5<4, 4, 2>".
+std::string label_of(const void* kernel) {
+  const char* mangled = hipKernelNameRefByPtr(kernel, nullptr);
+  if (!mangled) return "?";
+  // the C++ runtime's demangler may predate __bf16's code (DF16b): hand it the half type's (Dh; both are
+  // builtin types, so no substitution index moves; no kernel here takes a half) and rename it after
+  std::string m(mangled);
+  for (size_t a; (a = m.find("DF16b")) != std::string::npos;) m.replace(a, 5, "Dh");
+  int status = 0;
+  char* d = abi::__cxa_demangle(m.c_str(), nullptr, nullptr, &status);
+  std::string t(d && status == 0 ? d : mangled);
+  free(d);
+  for (size_t a; (a = t.find("half")) != std::string::npos;) t.replace(a, 4, "__bf16");
+  const std::string anon = "(anonymous namespace)::";
+  for (size_t a; (a = t.find(anon)) != std::string::npos;) t.erase(a, anon.size());
+  if (t.compare(0, 5, "void ") == 0) t.erase(0, 5);  // a template instantiation's return type
+  const size_t lt = t.find('<'), par = t.find('(');
+  if (lt != std::string::npos && lt < par) {  // keep through the '>' that closes the template arguments
+    int depth = 0;
+    for (size_t i = lt; i < t.size(); ++i) {
+      if (t[i] == '<') ++depth;
+      if (t[i] == '>' && --depth == 0) return t.substr(0, i + 1);
+    }
+  }
+  return t.substr(0, par);
+}
+
+// The launch log around one launcher call: log_begin empties the thread's ring, log_end appends what the
+// launcher noted (in launch order) to the handle's log.
+constexpr size_t kMaxLog = 1 << 16;  // a log nobody reads stops growing here
+void log_begin(const clasfv_engine* h) {
+  if (h->llog) g_launch_ring.n = 0;
+}
+void log_end(clasfv_engine* h, int conv) {
+  if (!h->llog) return;
+  const LaunchRing& r = g_launch_ring;
+  for (unsigned i = 0; i < r.n && i < 4 && h->log.size() < kMaxLog; ++i) {
+    auto it = h->labels.find(r.e[i].kernel);
+    if (it == h->labels.end()) it = h->labels.emplace(r.e[i].kernel, label_of(r.e[i].kernel)).first;
+    h->log.push_back({it->second.c_str(), r.e[i].grid, r.e[i].passes, conv});
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1137,7 +1201,9 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     side_join.pending = true;
     const int e0 = h->ktime ? tick(h, cx->side) : -1;
     const KernelInfo* k = nullptr;
+    log_begin(h);
     int rc_ = run_conv(c, xin, in, y, out, nullptr, false, cx->side, h->zero, x2, &k, h->tune);
+    log_end(h, conv_index(h, c));
     if (!rc_ && e0 >= 0) {
       const int e1 = tick(h, cx->side);
       if (e1 >= 0) h->recs.push_back({k->name, conv_gflop(c, out), k->xgflop(c, out), e0, e1});
@@ -1156,12 +1222,16 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
         scratch_bytes = mid_bytes - used;
       }
     }
+    log_begin(h);
     int rc_ = run_conv(c, xin, in, y, out, res, relu, s, h->zero, x2, &k, h->tune, x_c8, y_c8, scratch, scratch_bytes);
+    log_end(h, conv_index(h, c));
     if (!rc_) timed(k->name, conv_gflop(c, out), k->xgflop(c, out));
     return rc_;
   };
 
+  log_begin(h);
   HIP_TRY(launch_pack_input(x, reinterpret_cast<float*>(buf(XIN)), N, T, H * W, s));
+  log_end(h, -1);
   timed("pack_input_kernel", 0.0, 0.0);
   Shape5 sx{N, T, H, W, 4}, s0, sx0;
   Shape5 sp, sp2, sp3, sp4;  // decoder tap projections
@@ -1220,7 +1290,9 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   const float* tp[4];
   for (int i = 0; i < 4; ++i) tp[i] = reinterpret_cast<const float*>(buf(tb[i]));
   const DecParams d = decoder_params(h, tp, tsh, seg, mot, N, T, H, W, buf(DIDX));
+  log_begin(h);
   HIP_TRY(launch_decoder(d, s));
+  log_end(h, -1);
   // comb_2 (64x64) and the heads (6 useful of the 16 rows of their MFMA tile) per output voxel, in the
   // products of the pipe they run on: fp32 engines six split-bf16 products each (bf16 pipe), bf16
   // engines three for comb_2 and six for the heads (bf16 pipe), the no_decoder_x3 variant one f32
@@ -1267,6 +1339,28 @@ int clasfv_kernel_timing(clasfv_t h, int cap, const char** names, int* launches,
   return n;
 }
 
+int clasfv_set_launch_log(clasfv_t h, int enable) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  h->llog = enable != 0;
+  h->log.clear();
+  return CLASFV_OK;
+}
+
+int clasfv_launch_log(clasfv_t h, int cap, const char** labels, int64_t* grids, int* passes, int* convs) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  if (cap < 0 || (cap > 0 && (!labels || !grids || !passes || !convs))) return fail(CLASFV_EINVAL, "bad argument");
+  if (h->log.size() > (size_t)cap) return fail(CLASFV_EINVAL, "launch log: cap too small");
+  const int n = (int)h->log.size();
+  for (int i = 0; i < n; ++i) {
+    labels[i] = h->log[i].label;
+    grids[i] = h->log[i].grid;
+    passes[i] = h->log[i].passes;
+    convs[i] = h->log[i].conv;
+  }
+  h->log.clear();
+  return n;
+}
+
 // ---- diagnostics: one conv / the decoder alone, through the forward's own dispatch ---------------
 
 int clasfv_conv_count(clasfv_t h) { return h ? (int)h->convs.size() + 4 : CLASFV_EINVAL; }
@@ -1308,8 +1402,10 @@ int clasfv_run_conv(clasfv_t h, int i, const void* x, int N, int T, int H, int W
   const Shape5 in{N, T, H, W, c->cin_p};
   Shape5 out;
   const KernelInfo* k = nullptr;
+  log_begin(h);
   int rc = run_conv(*c, x, in, y, out, res, relu != 0, (hipStream_t)stream, h->zero, x2, &k, h->tune, x_c8, y_c8,
                     scratch_bytes ? scratch : nullptr, (size_t)scratch_bytes);
+  log_end(h, i);
   if (kernel_name) *kernel_name = k ? k->name : "";
   return rc;
 }
@@ -1339,7 +1435,9 @@ int clasfv_run_decoder(clasfv_t h, const float* p01, const float* p2, const floa
     if (k) t = half(t), hh = half(hh), ww = half(ww);
     tsh[k] = Shape5{N, t, hh, ww, 64};
   }
+  log_begin(h);
   HIP_TRY(launch_decoder(decoder_params(h, taps, tsh, seg, mot, N, T, H, W, cx->arena + L.off[DIDX]), s));
+  log_end(h, -1);
   return CLASFV_OK;
 }
 

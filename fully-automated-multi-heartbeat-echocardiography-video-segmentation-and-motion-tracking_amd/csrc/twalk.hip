@@ -262,8 +262,8 @@ hipError_t launch_tw_e(const ConvParams& p, hipStream_t s) {
   const long waves = (long)p.N * n_cols * n_seg;
   const size_t lds = 64 * tw_pitch(16 * CS) + 64 * 4 + 4 * 32 * TW_SP;
   const long blocks = (waves + 3) / 4;  // per half; HV = 2: 16 blocks per 8 block pairs
-  hipLaunchKernelGGL((conv_twalk_bf16<CS, TS, EF, PD, W, KO, HV>), dim3((unsigned)(HV == 2 ? (blocks + 7) / 8 * 16 : blocks)),
-                     dim3(256), lds, s, p, n_cols, n_seg);
+  CLASFV_LAUNCH((conv_twalk_bf16<CS, TS, EF, PD, W, KO, HV>),
+                dim3((unsigned)(HV == 2 ? (blocks + 7) / 8 * 16 : blocks)), dim3(256), lds, s, p, n_cols, n_seg);
   return hipGetLastError();
 }
 template <int CS, int TS, int HV>
@@ -606,8 +606,8 @@ hipError_t launch_tx_e(const ConvParams& p, hipStream_t s) {
   const long waves = (long)p.N * n_cols * n_seg;
   const size_t lds = 3 * 32 * tx_pitch(16 * CS) + 128 + 4 * W * 32 * TX_SP;
   const long pairs = (waves + 4 * W - 1) / (4 * W);  // blocks per channel half; 16 blocks per 8 pairs
-  hipLaunchKernelGGL((conv_twalk_x3<CS, TS, EF, XC8, W>), dim3((unsigned)((pairs + 7) / 8 * 16)), dim3(256 * W), lds, s, p,
-                     n_cols, n_seg);
+  CLASFV_LAUNCH((conv_twalk_x3<CS, TS, EF, XC8, W>), dim3((unsigned)((pairs + 7) / 8 * 16)), dim3(256 * W), lds, s, p,
+                n_cols, n_seg);
   return hipGetLastError();
 }
 template <int CS, int TS, bool XC8, int W>

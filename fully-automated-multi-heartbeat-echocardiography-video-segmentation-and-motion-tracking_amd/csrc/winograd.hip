@@ -333,11 +333,11 @@ hipError_t launch_wino(const ConvParams& p, hipStream_t s) {
   const int tx = (p.Wo + 1) / 2, ty = (p.Ho + 1) / 2;
   const FastDiv fd_f = fast_div(tx * ty), fd_x = fast_div(tx);
   switch (p.Cin >> 3) {  // fully unrolled chunk loops for the layer1..4 widths
-    case 8: hipLaunchKernelGGL((conv_wino<3, 8>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
-    case 16: hipLaunchKernelGGL((conv_wino<3, 16>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
-    case 32: hipLaunchKernelGGL((conv_wino<3, 32>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
-    case 64: hipLaunchKernelGGL((conv_wino<3, 64>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
-    default: hipLaunchKernelGGL((conv_wino<3, 0>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
+    case 8: CLASFV_LAUNCH((conv_wino<3, 8>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
+    case 16: CLASFV_LAUNCH((conv_wino<3, 16>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
+    case 32: CLASFV_LAUNCH((conv_wino<3, 32>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
+    case 64: CLASFV_LAUNCH((conv_wino<3, 64>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
+    default: CLASFV_LAUNCH((conv_wino<3, 0>), dim3(nb * n_co), dim3(256), 0, s, p, n_co, n_tiles, fd_f, fd_x); break;
   }
   return hipGetLastError();
 }
@@ -349,8 +349,8 @@ hipError_t launch_wino_ko(const ConvParams& p, hipStream_t s, int ko) {
   const int n_tiles = p.N * p.To * ((p.Ho + 1) / 2) * ((p.Wo + 1) / 2);
   const int n_co = p.Cout / 48;
   const int tx = (p.Wo + 1) / 2, ty = (p.Ho + 1) / 2;
-  hipLaunchKernelGGL((conv_wino<3, 0>), dim3(((n_tiles + BT - 1) / BT) * n_co), dim3(256), 0, s, p, n_co, n_tiles,
-                     fast_div(tx * ty), fast_div(tx));
+  CLASFV_LAUNCH((conv_wino<3, 0>), dim3(((n_tiles + BT - 1) / BT) * n_co), dim3(256), 0, s, p, n_co, n_tiles,
+                fast_div(tx * ty), fast_div(tx));
   return hipGetLastError();
 }
 #endif

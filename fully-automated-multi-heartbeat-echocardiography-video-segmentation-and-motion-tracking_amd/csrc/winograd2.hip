@@ -374,15 +374,15 @@ hipError_t launch_qe(const ConvParams& p, hipStream_t s) {
   const FastDiv fd_co = fast_div(n_co), fd_frame = fast_div(px * py), fd_px = fast_div(px);
   if constexpr (EPI == 2) {  // 8-channel-blocked output: the Conv2Plus1D spatial half (engine.hip, c8_pair)
     if (p.y_c8) {
-      hipLaunchKernelGGL((conv_wino_q<NCH, PT, EPI, true>), grid, dim3(256), 0, s, p, n_co, n_patches, fd_co, fd_frame,
-                         fd_px);
+      CLASFV_LAUNCH((conv_wino_q<NCH, PT, EPI, true>), grid, dim3(256), 0, s, p, n_co, n_patches, fd_co, fd_frame,
+                    fd_px);
       return hipGetLastError();
     }
   } else {
     if (p.y_c8) return hipErrorInvalidValue;
   }
-  hipLaunchKernelGGL((conv_wino_q<NCH, PT, EPI, false>), grid, dim3(256), 0, s, p, n_co, n_patches, fd_co, fd_frame,
-                     fd_px);
+  CLASFV_LAUNCH((conv_wino_q<NCH, PT, EPI, false>), grid, dim3(256), 0, s, p, n_co, n_patches, fd_co, fd_frame,
+                fd_px);
   return hipGetLastError();
 }
 

@@ -384,14 +384,14 @@ hipError_t launch_w4(const ConvParams& p, const W4Geo& g, int n_blocks, hipStrea
   const dim3 grid(n_blocks), block(W4_THREADS);
   if (p.y_c8) {
     if (p.relu)
-      hipLaunchKernelGGL((conv_wino4<NCH, true, true, DPW>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4<NCH, true, true, DPW>), grid, block, 0, s, p, g);
     else
-      hipLaunchKernelGGL((conv_wino4<NCH, true, false, DPW>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4<NCH, true, false, DPW>), grid, block, 0, s, p, g);
   } else {
     if (p.relu)
-      hipLaunchKernelGGL((conv_wino4<NCH, false, true, DPW>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4<NCH, false, true, DPW>), grid, block, 0, s, p, g);
     else
-      hipLaunchKernelGGL((conv_wino4<NCH, false, false, DPW>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4<NCH, false, false, DPW>), grid, block, 0, s, p, g);
   }
   return hipGetLastError();
 }
@@ -480,9 +480,9 @@ size_t wino4_weight_floats(int cin_p, int cout_p) {
 template <int KO>
 static hipError_t launch_w4ko(const ConvParams& p, const W4Geo& g, int nb, hipStream_t s) {
   if (p.Cin == 128)
-    hipLaunchKernelGGL((conv_wino4<16, false, true, 4, KO>), dim3(nb), dim3(W4_THREADS), 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4<16, false, true, 4, KO>), dim3(nb), dim3(W4_THREADS), 0, s, p, g);
   else
-    hipLaunchKernelGGL((conv_wino4<8, false, true, 4, KO>), dim3(nb), dim3(W4_THREADS), 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4<8, false, true, 4, KO>), dim3(nb), dim3(W4_THREADS), 0, s, p, g);
   return hipGetLastError();
 }
 hipError_t launch_wino4_ko(const ConvParams& p, hipStream_t s, int ko) {

@@ -827,22 +827,22 @@ hipError_t launch_w4r(const ConvParams& p, const W4Geo& g, int n_blocks, hipStre
   // winot 5.46 -> 5.38 ms per forward, step 21.57 -> 21.38 ms)
   if (!(p.vflags & CLASFV_VARIANT_W4R_CACHED_STORES)) {
     if (p.y_c8 && p.relu) {
-      hipLaunchKernelGGL((conv_wino4r<NTN, true, KO, true, NR, CPB, true>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, true, NR, CPB, true>), grid, block, 0, s, p, g);
       return hipGetLastError();
     }
     if (p.relu) {
-      hipLaunchKernelGGL((conv_wino4r<NTN, false, KO, true, NR, CPB, true>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, true, NR, CPB, true>), grid, block, 0, s, p, g);
       return hipGetLastError();
     }
   }
   if (p.y_c8 && p.relu)
-    hipLaunchKernelGGL((conv_wino4r<NTN, true, KO, true, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, true, NR, CPB>), grid, block, 0, s, p, g);
   else if (p.relu)
-    hipLaunchKernelGGL((conv_wino4r<NTN, false, KO, true, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, true, NR, CPB>), grid, block, 0, s, p, g);
   else if (p.y_c8)
-    hipLaunchKernelGGL((conv_wino4r<NTN, true, KO, false, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, false, NR, CPB>), grid, block, 0, s, p, g);
   else
-    hipLaunchKernelGGL((conv_wino4r<NTN, false, KO, false, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, false, NR, CPB>), grid, block, 0, s, p, g);
   return hipGetLastError();
 }
 
@@ -866,13 +866,13 @@ hipError_t launch_w4w(const ConvParams& p, const W4Geo& g, int n_blocks, hipStre
   const dim3 grid(n_blocks), block(W4_THREADS);
   // every Conv2Plus1D spatial half is followed by BN + ReLU: the ReLU form is the one that runs
   if (p.y_c8 && p.relu)
-    hipLaunchKernelGGL((conv_wino4w<NTN, true, DPW, KO, true>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4w<NTN, true, DPW, KO, true>), grid, block, 0, s, p, g);
   else if (p.relu)
-    hipLaunchKernelGGL((conv_wino4w<NTN, false, DPW, KO, true>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4w<NTN, false, DPW, KO, true>), grid, block, 0, s, p, g);
   else if (p.y_c8)
-    hipLaunchKernelGGL((conv_wino4w<NTN, true, DPW, KO, false>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4w<NTN, true, DPW, KO, false>), grid, block, 0, s, p, g);
   else
-    hipLaunchKernelGGL((conv_wino4w<NTN, false, DPW, KO, false>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4w<NTN, false, DPW, KO, false>), grid, block, 0, s, p, g);
   return hipGetLastError();
 }
 

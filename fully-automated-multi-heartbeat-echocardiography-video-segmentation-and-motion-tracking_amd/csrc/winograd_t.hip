@@ -518,8 +518,8 @@ hipError_t winot5_launch_e(const ConvParams& p, hipStream_t s) {
   const int n_seg = (p.Ti / 4) / TS;
   const int n_co = p.Cout / G::CB;
   const int nb = ((n_cols + G::P - 1) / G::P) * n_seg * n_co * ((EPI & 4) ? p.n_split : 1);
-  hipLaunchKernelGGL((conv_winot5<TS, NT, EPI>), dim3(nb), dim3(256), G::LDS, s, p, n_co, n_seg, n_cols,
-                     fast_div(p.Hi * p.Wi));
+  CLASFV_LAUNCH((conv_winot5<TS, NT, EPI>), dim3(nb), dim3(256), G::LDS, s, p, n_co, n_seg, n_cols,
+                fast_div(p.Hi * p.Wi));
   return hipGetLastError();
 }
 
@@ -622,7 +622,7 @@ hipError_t launch_winot(const ConvParams& p, hipStream_t s) {
   const int n_tiles = p.N * (p.Ti / 4) * p.Hi * p.Wi;
   const int n_co = p.Cout / BN;
   const int nb = (n_tiles + BT - 1) / BT;
-  hipLaunchKernelGGL(conv_winot, dim3(nb * n_co), dim3(NTHR), LDS_BYTES, s, p, n_co, n_tiles);
+  CLASFV_LAUNCH(conv_winot, dim3(nb * n_co), dim3(NTHR), LDS_BYTES, s, p, n_co, n_tiles);
   return hipGetLastError();
 }
 
@@ -636,8 +636,8 @@ hipError_t launch_winot_ko(const ConvParams& p, hipStream_t s, int ko) {
       hipError_t e = hipFuncSetAttribute((const void*)conv_winot, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
       if (e != hipSuccess) return e;
       const int n_tiles = p.N * (p.Ti / 4) * p.Hi * p.Wi;
-      hipLaunchKernelGGL(conv_winot, dim3(((n_tiles + BT - 1) / BT) * (p.Cout / BN)), dim3(NTHR), LDS_BYTES, s, p,
-                         p.Cout / BN, n_tiles);
+      CLASFV_LAUNCH(conv_winot, dim3(((n_tiles + BT - 1) / BT) * (p.Cout / BN)), dim3(NTHR), LDS_BYTES, s, p,
+                    p.Cout / BN, n_tiles);
       return hipGetLastError();
     }
     case 500: return p.x_c8 && !winot_c8_ok(p) ? hipErrorInvalidValue : winot5_dispatch(p, s);

@@ -124,6 +124,24 @@ class Engine:
         _lib.check(self.lib.clasfv_run_decoder(self.h, *[_lib.ptr(a) for a in taps], n, t, hh, ww, _lib.ptr(seg),
                                                _lib.ptr(mot), _lib.stream_ptr(stream, self.device)), "clasfv_run_decoder")
 
+    def set_launch_log(self, enable=True):
+        """Record every kernel launch of later forward / run_conv / run_decoder calls (clasfv_launch_log)."""
+        _lib.check(self.lib.clasfv_set_launch_log(self.h, 1 if enable else 0), "clasfv_set_launch_log")
+
+    def launch_log(self, cap=4096):
+        """[(label, grid, passes, conv)] of the launches since the last call, in order (then cleared).
+        label: the instantiation as the compiler spells it, e.g. "conv_winot5<4, 4, 2>" (an opaque key; the
+        part before "<" is the kernel's name); passes: work items per wave or block of a capped grid, else 1;
+        conv: clasfv_conv_info's index, -1 for pack_input_kernel and the decoder."""
+        labels = (ctypes.c_char_p * cap)()
+        grids = (ctypes.c_int64 * cap)()
+        passes = (ctypes.c_int * cap)()
+        convs = (ctypes.c_int * cap)()
+        n = self.lib.clasfv_launch_log(self.h, cap, labels, grids, passes, convs)
+        if n < 0:
+            _lib.check(n, "clasfv_launch_log")
+        return [(labels[i].decode(), int(grids[i]), int(passes[i]), int(convs[i])) for i in range(n)]
+
     def set_kernel_timing(self, enable=True):
         """Per-kernel HIP-event timing of every later forward (see clasfv_kernel_timing)."""
         _lib.check(self.lib.clasfv_set_kernel_timing(self.h, 1 if enable else 0), "clasfv_set_kernel_timing")

@@ -144,6 +144,23 @@ int clasfv_set_kernel_timing(clasfv_t h, int enable);
 int clasfv_kernel_timing(clasfv_t h, int cap, const char** names, int* launches, double* ms,
                          double* gflop, double* xgflop);
 
+/* ---- diagnostics: the launch log (new exports only: the ABI revision is unchanged) ------------ */
+/* enable != 0: every later clasfv_forward, clasfv_run_conv and clasfv_run_decoder on this handle records
+ * each kernel it launches. Enabling or disabling drops what was recorded. Off (the default), a launch
+ * costs a few host stores more than without the log. */
+int clasfv_set_launch_log(clasfv_t h, int enable);
+/* The launches recorded since the last call, in launch order, and clears them. Entry i: labels[i], the
+ * instantiation launched as the compiler spells it (e.g. "conv_winot5<4, 4, 2>"; a string owned by the
+ * handle, valid until clasfv_destroy; derived from the kernel's address at the launch site, never typed
+ * by hand: treat it as an opaque key whose part before '<' is the kernel's name); grids[i], its blocks;
+ * passes[i], the largest number of work items one wave or block of the launch processes in turn (1
+ * unless the launcher caps its grid: conv_stem_x3, conv_stem_bf16, conv_proj_x3, pack_input_kernel);
+ * convs[i], the conv it belongs to (clasfv_conv_info's numbering; a split-K launch and its
+ * split_sum_kernel share one) or -1 for pack_input_kernel and the decoder's kernels. Returns the number
+ * of entries; CLASFV_EINVAL, with the log kept, when more than cap are waiting. At most 65536 launches
+ * are kept between two calls. */
+int clasfv_launch_log(clasfv_t h, int cap, const char** labels, int64_t* grids, int* passes, int* convs);
+
 /* ---- diagnostics: one layer alone (for layer-level tests; not on the reference's interface) - */
 /* New exports only: the ABI revision is unchanged. Convs are numbered in execution order: the
  * backbone's (stem.0, stem.3, layer1.0.conv1.0.0, ...), then the decoder's tap projections P01 (dual

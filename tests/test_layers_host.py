@@ -99,3 +99,15 @@ def test_diagnostic_entries_reject_a_null_handle():
                                None) == -1
     assert lib.clasfv_run_decoder(None, None, None, None, None, 1, 8, 16, 16, None, None, None) == -1
     assert b"null handle" in lib.clasfv_last_error()
+
+
+def test_launch_log_entries_reject_a_null_handle():
+    from clasfv_amd import _lib
+    lib = _lib.load()
+    assert lib.clasfv_set_launch_log(None, 1) == -1
+    assert b"null handle" in lib.clasfv_last_error()
+    labels, grids = (ctypes.c_char_p * 4)(), (ctypes.c_int64 * 4)()
+    passes, convs = (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
+    assert lib.clasfv_launch_log(None, 4, labels, grids, passes, convs) == -1
+    assert b"null handle" in lib.clasfv_last_error()
+    assert lib.clasfv_launch_log(None, 0, None, None, None, None) == -1
