@@ -19,11 +19,16 @@ struct W4Geo {
   int n_cob;    // output-channel blocks (cob_w channels each) per tile group
   int gpr;      // groups per flattened tile row (TW / TC)
   FastDiv fd_cob, fd_gpr, fd_th, fd_tc, fd_rp, fd_ss;
-#ifdef CLASFV_KNOCKOUTS
-  // conv_wino4r start stagger (convbench probe, profiles/r05ag_*: ±0): first-round block b waits
-  // ((b / 8) % stagger_groups) * stagger ticks of the 100-MHz real-time clock before its first DMA
+  // line stages (conv_wino4r): a pixel's 128-B line (32 input channels = 4 chunks) is 8 consecutive slots,
+  // with a pad slot after every 4 pixels
+  int LRP;      // slots per raw patch row (8 (4 TC + 2) + TC)
+  int LSS;      // slots per segment (>= 6 LRP, searched: the 16 tiles of a read on 16 distinct bank quads)
+  int LSL;      // slots per stage ((TR - 1) LSS + 6 LRP)
+  int LNI;      // DMA wave-instructions per stage (ceil(LSL / 64)); a stage is LNI KiB
+  FastDiv fd_lrp, fd_lss;
+  // conv_wino4r start stagger (launch_wino4r): first-round block b waits ((b / 8) % stagger_groups) *
+  // stagger ticks of the 100-MHz real-time clock before its first DMA (0: none)
   int stagger, stagger_groups;
-#endif
 };
 
 namespace {
@@ -100,10 +105,8 @@ __device__ inline void bt_cols(const f32x2 (&t)[6], f32x2 (&v)[3]) {
 // At 56x56 maps (TW = 14) that is 8 rows x 2 tiles instead of 1 x 14: 16 of 16 MFMA rows carry tiles
 // instead of 14, for 20 % more raw-patch bytes per tile.
 inline bool wino4_geometry(const ConvParams& p, W4Geo* g, int* n_blocks, int cob_w = 48, int fill16 = 0) {
-#ifdef CLASFV_KNOCKOUTS
   g->stagger = 0;
   g->stagger_groups = 1;
-#endif
   if (p.Cout % cob_w || p.Cin % 8) return false;
   const int TH = (p.Ho + 3) / 4, TW = (p.Wo + 3) / 4;
   const long rows = (long)p.N * p.To * TH;  // flattened tile rows
@@ -158,6 +161,18 @@ inline bool wino4_geometry(const ConvParams& p, W4Geo* g, int* n_blocks, int cob
   g->fd_tc = fast_div(TC);
   g->fd_rp = fast_div(g->RP);
   g->fd_ss = fast_div(g->SS);
+  // line stages: tile (seg, col) reads slot seg LSS + 33 col + (a constant per instruction), so the
+  // smallest LSS >= 6 LRP with seg LSS + col distinct mod 16 (LSS = TC mod 16 always is) has no bank conflict
+  g->LRP = 8 * (4 * TC + 2) + TC;
+  for (g->LSS = 6 * g->LRP;; ++g->LSS) {
+    unsigned seen = 0;
+    for (int t = 0; t < TR * TC; ++t) seen |= 1u << (((t / TC) * g->LSS + 33 * (t % TC)) & 15);
+    if (__builtin_popcount(seen) == TR * TC) break;
+  }
+  g->LSL = (TR - 1) * g->LSS + 6 * g->LRP;
+  g->LNI = (g->LSL + 63) / 64;
+  g->fd_lrp = fast_div(g->LRP);
+  g->fd_lss = fast_div(g->LSS);
   *n_blocks = (int)(rows / TR) * g->gpr * g->n_cob;
   return true;
 }

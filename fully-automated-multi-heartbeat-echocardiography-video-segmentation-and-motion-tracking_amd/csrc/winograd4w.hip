@@ -426,12 +426,17 @@ __global__ __launch_bounds__(W4_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
 // quadrant's row transform).
 constexpr int W4R_WAVES = 12;
 constexpr int W4R_THREADS = 64 * W4R_WAVES;
-constexpr int W4R_DPW = 2;  // DMA instructions per wave per ring stage (wino4_geometry: NI <= 24)
-constexpr int W4R_STAGE = W4R_WAVES * W4R_DPW * 1024;
-constexpr int W4R_NR = 4;  // raw ring stages (a barrier every NR / 2 chunks)
+// Raw ring: two LINE stages. A stage holds four chunks (32 input channels) of the patch, a pixel's
+// 128-B line as 8 consecutive 16-B slots (W4Geo::LRP / LSS / LSL / LNI): 8 consecutive DMA lanes fetch
+// one whole line, each line is requested once per block, and chunk k reads its 32 B at k % 4 * 32 inside
+// the pixel's row (chunk order, K order and products as before). The stage is LNI KiB (16 x 1 tile groups:
+// 74, 8 x 2: 62), a barrier every 4 chunks; at Cin = 64 the two stages are the whole patch.
+constexpr int W4R_DPW = 7;  // DMA instructions per wave per stage (LNI <= 79 <= 84; the rest go to the sink)
+constexpr int W4R_NR = 2;   // stages
 constexpr int W4R_NZ = 3;  // epilogue plane buffers = N tiles per epilogue round
 constexpr int W4R_LDS = W4R_NZ * W4W_ZBUF * 4;  // 163,296 B
-static_assert(W4R_LDS >= W4R_NR * W4R_STAGE + 1024 && W4R_LDS <= 160 * 1024, "ring and planes fit LDS");
+constexpr int W4R_MAX_LNI = (W4R_LDS - 1024) / (W4R_NR * 1024);  // 79: two stages and the sink inside the planes
+static_assert(W4R_MAX_LNI <= W4R_WAVES * W4R_DPW && W4R_LDS <= 160 * 1024, "ring and planes fit LDS");
 
 // per wave and chunk: NV = 3 elements x 2 K steps x NTN U values, m = (nt * 2 + ks) * 3 + jj, as NU f32x4
 // loads through a UQ-deep register ring
@@ -470,26 +475,25 @@ __device__ inline f32x2 bt_row(const f32x2 (&e)[5]) {
 
 // KO (tools/convbench diagnostics, 0 in the product; results wrong otherwise): 1 no transform, 2 no U
 // loads in the loop, 4 no epilogue, 8 no loop DMAs, 16 no chunk barriers, 128 no output stores, 512
-// per-block phase stamps (as conv_wino4w's). NR: raw ring stages (4: a barrier every 2 chunks; 6: every 3)
-template <int NTN, bool C8, int KO = 0, bool RELU = true, int NR = W4R_NR, int CPB = 1, bool NTS = false>
+// per-block phase stamps (as conv_wino4w's).
+template <int NTN, bool C8, int KO = 0, bool RELU = true, int CPB = 1, bool NTS = false>
 __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_wino4r(ConvParams p,
                                                                                                        W4Geo g) {
   using WR = W4R<NTN>;
-  constexpr int STAGE = W4R_STAGE, UQ = WR::UQ, NU = WR::NU, NV = WR::NV;
-  constexpr int STEP = NR / 2;  // chunks per barrier: raw(k) .. raw(k + STEP - 1) land STEP chunks ahead
-  static_assert(NR * STAGE + 1024 <= W4R_LDS, "ring fits the plane buffers' LDS");
+  constexpr int UQ = WR::UQ, NU = WR::NU, NV = WR::NV;
   __shared__ __align__(16) char smem[W4R_LDS];
-  char* sink = smem + NR * STAGE;
+  const int STAGE = g.LNI * 1024;  // <= W4R_MAX_LNI KiB (wino4r_supported)
+  char* sink = smem + W4R_NR * STAGE;
 
 #ifdef CLASFV_KNOCKOUTS
   unsigned long long st_[4] = {0, 0, 0, 0};
   if constexpr ((KO & 512) != 0) st_[0] = __builtin_amdgcn_s_memrealtime();
 #endif
-#ifdef CLASFV_KNOCKOUTS
-  // (convbench only) start stagger (W4Geo::stagger): blocks of equal work started together stay in lockstep, and all
-  // 256 CUs then run their epilogues -- the output stores -- at once, reading nothing meanwhile
-  // (profiles/r05ag_wino4r_epilogue_concurrency.txt); first-round blocks 8 j .. 8 j + 7 (one per XCD)
-  // start (j % groups) stagger ticks apart, so the epilogues of different CUs fall in different phases
+  // start stagger (W4Geo::stagger, set by launch_wino4r on long grids): blocks of equal work started together
+  // stay in lockstep, and all 256 CUs then run their epilogues -- the output stores -- at once, reading
+  // nothing meanwhile (profiles/r05ag_wino4r_epilogue_concurrency.txt); first-round blocks 8 j .. 8 j + 7
+  // (one per XCD) start (j % groups) stagger ticks apart, so the epilogues of different CUs fall in
+  // different phases of a block's period
   if (g.stagger > 0 && blockIdx.x < 256) {
     const int sg = (blockIdx.x >> 3) % g.stagger_groups;
     if (sg) {
@@ -497,7 +501,6 @@ __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
       while (__builtin_amdgcn_s_memrealtime() - t0 < dt) __builtin_amdgcn_s_sleep(8);
     }
   }
-#endif
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(p.x), (short)0, (int)((size_t)p.N * p.Ti * p.Hi * p.Wi * p.Cin * 4), 0x00020000);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -512,49 +515,57 @@ __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
   // wave (rh, ch, r) = wid / 6, (wid / 3) % 2, wid % 3
   const int wq = wid / 3, r = wid - 3 * wq, rh = wq >> 1, ch = wq & 1;
 
-  // ---- LDS-DMA slot table (conv_wino4w's, over 12 waves): instruction j of this wave fills slots
-  // (wid + 12 j) * 64 + lane of a stage
-  unsigned d_off[W4R_DPW];
+  // ---- LDS-DMA slot table: instruction j of this wave fills slots (wid + 12 j) * 64 + lane of a stage.
+  // Slot = seg * LSS + r * LRP + cs (window row r < 6 of segment seg); cs = 33 m + q: pixel column
+  // 4 m + q / 8, 16-B part q % 8 of its line (input channels 4 (q % 8) .. + 3 of the stage's 32), q = 32: pad
+  unsigned d_off[W4R_DPW];  // byte offset of the slot's 16 B in stage 0, or 0x80000000 (zeros)
 #pragma unroll
   for (int j = 0; j < W4R_DPW; ++j) {
-    const int ins = wid + W4R_WAVES * j, s = ins * 64 + lane;
+    const int s = (wid + W4R_WAVES * j) * 64 + lane;
     unsigned off = 0x80000000u;
-    if (ins < g.NI && s < 2 * g.RS) {
-      const int hf = s >= g.RS ? 1 : 0, sl = s - hf * g.RS;
-      const int seg = fdiv(sl, g.fd_ss), ss = sl - seg * g.SS;
-      const int rr = fdiv(ss, g.fd_rp), cs = ss - rr * g.RP;
-      const int m5 = cs / 5, k5 = cs - 5 * m5, c = 4 * m5 + k5;
-      if (rr < 6 && k5 < 4 && c < 4 * g.TC + 2) {
+    if (s < g.LSL) {
+      const int seg = fdiv(s, g.fd_lss), ss = s - seg * g.LSS;
+      const int rr = fdiv(ss, g.fd_lrp), cs = ss - rr * g.LRP;
+      const int m33 = cs / 33, q33 = cs - 33 * m33, c = 4 * m33 + (q33 >> 3), part = q33 & 7;
+      if (rr < 6 && q33 < 32 && c < 4 * g.TC + 2 && 4 * part < C) {
         const int R = R0 + seg, f = fdiv(R, g.fd_th), ty = R - f * g.TH;
         const int yy = 4 * ty - 1 + rr, xx = 4 * tx0 - 1 + c;
-        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) off = (((f * H + yy) * W + xx) * C + hf * 4) * 4;
+        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) off = (((f * H + yy) * W + xx) * C + 4 * part) * 4;
       }
     }
     d_off[j] = off;
   }
-  auto issue_raw = [&](int k, int stage) __attribute__((always_inline)) {
+  // stage S = input channels 32 S .. 32 S + 31 into ring buffer buf. The stage's byte offset goes into
+  // the lane offsets, where the buffer resource bounds it (a last stage of fewer than four chunks
+  // fetches, and never reads, the bytes after its channels: the next pixel's, or zeros past the
+  // tensor); a stage past the last channel fetches nothing. Every wave issues W4R_DPW DMAs either way.
+  auto issue_raw = [&](int S, int buf) __attribute__((always_inline)) {
+    const bool live = 32 * S < C;
 #pragma unroll
     for (int j = 0; j < W4R_DPW; ++j) {
       const int ins = wid + W4R_WAVES * j;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          xr, (__attribute__((address_space(3))) void*)(ins < g.NI ? smem + stage * STAGE + ins * 1024 : sink), 16,
-          d_off[j], k < nchunk ? k * 32 : 0, 0, 0);
+          xr, (__attribute__((address_space(3))) void*)(ins < g.LNI ? smem + buf * STAGE + ins * 1024 : sink), 16,
+          live ? d_off[j] + 128u * S : 0x80000000u, 0, 0, 0);
     }
   };
 
-  // ---- transform lane: tile t, channel pair k4 (conv_wino4w's); this wave's row of B^T d B
+  // ---- transform lane: tile t, channel pair k4 (conv_wino4w's); this wave's row of B^T d B. Window
+  // pixel (q, c) of the tile is at slot q * LRP + 8 c + c / 4 from the tile's first; chunk kc of the stage
+  // and channel pair k4 at byte 32 kc + 8 k4 of the pixel's row. The 16 tiles of a 32-lane read group
+  // sit at slots seg * LSS + 33 col: 16 distinct bank quads (wino4_geometry)
   const int t = lane & 15, k4 = lane >> 4;
   const int tv = t < NT ? t : 0;
   const int tseg = fdiv(tv, g.fd_tc), tcol = tv - tseg * g.TC;
-  const int lane_off = ((k4 >> 1) * g.RS + tseg * g.SS + rh * g.RP + 5 * tcol) * 16 + (k4 & 1) * 8;
-  const int rp16 = g.RP * 16;
-  auto transform = [&](int stage, f32x2 (&a)[3]) __attribute__((always_inline)) {
+  const int lane_off = (tseg * g.LSS + rh * g.LRP + 33 * tcol) * 16 + k4 * 8;
+  const int rp16 = g.LRP * 16;
+  auto transform = [&](int buf, int kc, f32x2 (&a)[3]) __attribute__((always_inline)) {
     if constexpr ((KO & 1) != 0) {
 #pragma unroll
-      for (int jj = 0; jj < 3; ++jj) a[jj] = f32x2{(float)(lane + jj + stage), (float)(lane - jj)};
+      for (int jj = 0; jj < 3; ++jj) a[jj] = f32x2{(float)(lane + jj + buf + kc), (float)(lane - jj)};
       return;
     }
-    const char* base = smem + stage * STAGE + lane_off;
+    const char* base = smem + buf * STAGE + kc * 32 + lane_off;
     auto body = [&](auto rh_c, auto ch_c, auto r_c) __attribute__((always_inline)) {
       constexpr int RH = decltype(rh_c)::value, CH = decltype(ch_c)::value, RR = decltype(r_c)::value;
       f32x2 tt[6];
@@ -562,7 +573,7 @@ __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
         // software-pipelined: column c + 1's window reads are issued before column c's row transform,
         // so one LDS round trip is exposed per chunk instead of six (two columns' reads live at once)
         auto col_read = [&](int c, f32x2 (&e)[5]) __attribute__((always_inline)) {
-          const int co = (c + (c >> 2)) * 16;
+          const int co = (8 * c + (c >> 2)) * 16;
 #pragma unroll
           for (int q = 0; q < 5; ++q) e[q] = *reinterpret_cast<const f32x2*>(base + q * rp16 + co);
         };
@@ -581,7 +592,7 @@ __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
       } else {
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-          const int co = (c + (c >> 2)) * 16;  // pixel columns 0..5 of the window -> slots 0,1,2,3,5,6
+          const int co = (8 * c + (c >> 2)) * 16;  // pixel columns 0..5 of the window -> slots 0, 8, 16, 24, 33, 41
           f32x2 e[5];
 #pragma unroll
           for (int q = 0; q < 5; ++q) e[q] = *reinterpret_cast<const f32x2*>(base + q * rp16 + co);
@@ -629,38 +640,45 @@ __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
   f32x4 u[UQ];
   f32x2 a[3];
 
+  // ---- prologue: both stages' DMAs (at Cin = 64 the whole patch), then the first UQ U groups; stage 0
+  // has landed when at most stage 1's DMAs and those U loads are outstanding
 #pragma unroll
-  for (int d = 0; d < STEP; ++d) {
+  for (int d = 0; d < W4R_NR; ++d) {
     issue_raw(d, d);
     __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int gi = 0; gi < UQ; ++gi) u[gi] = load_u(0, gi);
   __builtin_amdgcn_sched_barrier(0);
+  static_assert(W4R_DPW + UQ <= 63, "vmcnt field");
+  __builtin_amdgcn_s_waitcnt(vm_wait(W4R_DPW + UQ));
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr ((KO & 16) == 0) __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+#ifdef CLASFV_KNOCKOUTS
+  if constexpr ((KO & 512) != 0) st_[1] = __builtin_amdgcn_s_memrealtime();
+#endif
 
-  // the ring and wait rule of conv_wino4w at NR = 4: every 2 chunks a barrier, then raw(k + 2),
-  // raw(k + 3) into the stages of chunks k - 2, k - 1; at most UQ VMEM ops outstanding at the wait
-  // (the U loads issued after raw(k + 1) on chunk 0, 2 NU later) leaves raw(k), raw(k + 1) landed
+  // chunk k reads part k % 4 of stage k / 4 in buffer (k / 4) % 2. At a stage's first chunk (k > 0) a
+  // barrier: every wave has read stage k / 4 - 1, whose buffer is refilled with stage k / 4 + 1 (none
+  // past the last channel: a wave's DMA count then differs from chunk to chunk, which the wait allows);
+  // this stage's own DMAs are older than the last UQ U loads (issued a stage, or the prologue, ago), so
+  // at most UQ VMEM ops outstanding leaves them landed
   int k = 0;
 #pragma unroll 1
   do {
-    const int ph = k % NR;
-    if (ph % STEP == 0) {
+    const int kc = k & 3, S = k >> 2, buf = S & 1;
+    if (kc == 0 && k > 0) {
       __builtin_amdgcn_s_waitcnt(vm_wait(UQ));
       __builtin_amdgcn_sched_barrier(0);
       if constexpr ((KO & 16) == 0) __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-#ifdef CLASFV_KNOCKOUTS
-      if constexpr ((KO & 512) != 0)
-        if (k == 0) st_[1] = __builtin_amdgcn_s_memrealtime();
-#endif
       if constexpr ((KO & 8) == 0) {
-#pragma unroll
-        for (int d = NR - STEP; d < NR; ++d) issue_raw(k + d, (ph + d) % NR);
+        if (32 * (S + 1) < C) issue_raw(S + 1, buf ^ 1);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    transform(ph, a);
+    transform(buf, kc, a);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int gi = 0; gi < NU; ++gi) {
@@ -818,7 +836,7 @@ __global__ __launch_bounds__(W4R_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
 #endif
 }
 
-template <int NTN, int KO = 0, int NR = W4R_NR, int CPB = 1>
+template <int NTN, int KO = 0, int CPB = 1>
 hipError_t launch_w4r(const ConvParams& p, const W4Geo& g, int n_blocks, hipStream_t s) {
   const dim3 grid(n_blocks), block(W4R_THREADS);
   // non-temporal output stores unless CLASFV_VARIANT_W4R_CACHED_STORES (the ReLU / C8 forms the forward
@@ -827,22 +845,22 @@ hipError_t launch_w4r(const ConvParams& p, const W4Geo& g, int n_blocks, hipStre
   // winot 5.46 -> 5.38 ms per forward, step 21.57 -> 21.38 ms)
   if (!(p.vflags & CLASFV_VARIANT_W4R_CACHED_STORES)) {
     if (p.y_c8 && p.relu) {
-      CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, true, NR, CPB, true>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, true, CPB, true>), grid, block, 0, s, p, g);
       return hipGetLastError();
     }
     if (p.relu) {
-      CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, true, NR, CPB, true>), grid, block, 0, s, p, g);
+      CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, true, CPB, true>), grid, block, 0, s, p, g);
       return hipGetLastError();
     }
   }
   if (p.y_c8 && p.relu)
-    CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, true, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, true, CPB>), grid, block, 0, s, p, g);
   else if (p.relu)
-    CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, true, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, true, CPB>), grid, block, 0, s, p, g);
   else if (p.y_c8)
-    CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, false, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, true, KO, false, CPB>), grid, block, 0, s, p, g);
   else
-    CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, false, NR, CPB>), grid, block, 0, s, p, g);
+    CLASFV_LAUNCH((conv_wino4r<NTN, false, KO, false, CPB>), grid, block, 0, s, p, g);
   return hipGetLastError();
 }
 
@@ -976,7 +994,18 @@ bool wino4r_supported(const ConvParams& p) {
          p.sh == 1 && p.sw == 1 && p.st == 1 && p.ph == 1 && p.pw == 1 && p.pt == 0 && p.Ho == p.Hi &&
          p.Wo == p.Wi && p.To == p.Ti &&
          (size_t)p.N * p.To * p.Ho * p.Wo * (p.Cin > p.Cout ? p.Cin : p.Cout) < ((size_t)1 << 31) &&
-         wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL);
+         wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL) && g.LNI <= W4R_MAX_LNI;  // (every group of <= 16 tiles: <= 74)
+}
+
+// Start stagger of a launch: on grids of >= 16 blocks per CU (layer1 at >= 11 clips of 32 x 112 x 112) the
+// first round's blocks start in 8 phases spread over one block period, modelled as 13.7 us of prologue and
+// epilogue + 2.64 us per chunk at NTN = 9 (layer1: 34.8 us measured, 4.35 us per phase; convbench 1.60 ->
+// 1.49 ms at 3.75 and 4.5 us, nothing at 3.0 or 5.25; shorter grids only lose the delay:
+// profiles/r08_wino4r_line_ring.txt).
+static void w4r_stagger(const ConvParams& p, int ntn, int n_blocks, W4Geo* g) {
+  if (n_blocks < 16 * 256) return;
+  g->stagger_groups = 8;
+  g->stagger = (1370 + 264 * (p.Cin / 8) * ntn / 9) / 8;  // ticks of 10 ns
 }
 
 // conv_wino4r (12 row waves per block) on conv_wino4w's tile groups; p.w: wino4r_transform_weights' layout.
@@ -986,6 +1015,7 @@ hipError_t launch_wino4r(const ConvParams& p, hipStream_t s) {
   int nb;
   const int ntn = wino4r_ntn(p.Cout);
   wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL);
+  w4r_stagger(p, ntn, nb, &g);
   return ntn == 9 ? launch_w4r<9>(p, g, nb, s) : launch_w4r<6>(p, g, nb, s);
 }
 
@@ -1061,7 +1091,7 @@ hipError_t launch_wino4w_ko(const ConvParams& p, hipStream_t s, int ko) {
     default: return launch_w4w_dpw<9>(p, g, nb, s);
   }
 }
-// tools/convbench: conv_wino4r diagnostics (KO bits of conv_wino4r; 64: the 6-stage ring), NTN = 9 only
+// tools/convbench: conv_wino4r diagnostics (KO bits of conv_wino4r), NTN = 9 only
 hipError_t launch_wino4r_ko(const ConvParams& p, hipStream_t s, int ko) {
   if (!wino4w_supported(p) || wino4w_ntn(p.Cout) != 9) return hipErrorInvalidValue;
   W4Geo g;
@@ -1077,12 +1107,10 @@ hipError_t launch_wino4r_ko(const ConvParams& p, hipStream_t s, int ko) {
     case 4: return launch_w4r<9, 4>(p, g, nb, s);
     case 128: return launch_w4r<9, 128>(p, g, nb, s);
     case 512: return launch_w4r<9, 512>(p, g, nb, s);
-    case 64: return launch_w4r<9, 0, 6>(p, g, nb, s);     // 6-stage ring, a barrier every 3 chunks
-    case 32: return launch_w4r<9, 0, 4, 2>(p, g, nb, s);  // 2 window columns' LDS reads in flight
-    case 96: return launch_w4r<9, 0, 4, 3>(p, g, nb, s);  // 3
-    case 160: return launch_w4r<9, 0, 4, 0>(p, g, nb, s);  // software-pipelined column reads
+    case 32: return launch_w4r<9, 0, 2>(p, g, nb, s);  // 2 window columns' LDS reads in flight
+    case 96: return launch_w4r<9, 0, 3>(p, g, nb, s);  // 3
+    case 160: return launch_w4r<9, 0, 0>(p, g, nb, s);  // software-pipelined column reads
     case 2048: return launch_w4r<9, 2048>(p, g, nb, s);    // non-temporal output stores
-    case 576: return launch_w4r<9, 512, 6>(p, g, nb, s);  // the same with stamps
     default: return launch_w4r<9>(p, g, nb, s);
   }
 }
