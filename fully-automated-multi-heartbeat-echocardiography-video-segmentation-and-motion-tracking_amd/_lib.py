@@ -34,6 +34,7 @@ SIGNATURES = {
     "clasfv_set_launch_log": (c_int, [_P, c_int]),
     "clasfv_launch_log": (c_int, [_P, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int64), ctypes.POINTER(c_int),
                                   ctypes.POINTER(c_int)]),
+    "clasfv_fill_workspace": (c_int, [_P, c_int, _P]),
     "clasfv_conv_count": (c_int, [_P]),
     "clasfv_conv_info": (c_int, [_P, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_char_p), ctypes.POINTER(c_int),
                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),

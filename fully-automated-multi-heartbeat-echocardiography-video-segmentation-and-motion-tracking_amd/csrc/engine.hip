@@ -1152,7 +1152,8 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   if (!h) return fail(CLASFV_EINVAL, "null handle");
   if (!h->ready) return fail(CLASFV_ENOTREADY, "clasfv_finalize has not been called");
   if (!x || !seg || !mot) return fail(CLASFV_EINVAL, "null tensor");
-  if (N < 1 || T < 8 || H < 16 || W < 16 || T % 8 || H % 16 || W % 16)
+  if (N < 1) return fail(CLASFV_EINVAL, "N must be >= 1");
+  if (T < 8 || H < 16 || W < 16 || T % 8 || H % 16 || W % 16)
     return fail(CLASFV_EBADSHAPE, "shape must satisfy T % 8 == 0, H % 16 == 0, W % 16 == 0 (got T=" +
                                       std::to_string(T) + " H=" + std::to_string(H) + " W=" + std::to_string(W) + ")");
   hipStream_t s = (hipStream_t)stream;
@@ -1359,6 +1360,19 @@ int clasfv_launch_log(clasfv_t h, int cap, const char** labels, int64_t* grids, 
   }
   h->log.clear();
   return n;
+}
+
+int clasfv_fill_workspace(clasfv_t h, int byte, void* stream) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  if (byte < 0 || byte > 255) return fail(CLASFV_EINVAL, "fill byte must be in [0, 255]");
+  hipStream_t s = (hipStream_t)stream;
+  clasfv_engine::Ctx* cx = nullptr;
+  for (auto* c : h->ctxs)
+    if (c->stream == s) cx = c;
+  if (!cx || !cx->arena) return fail(CLASFV_EINVAL, "no workspace exists for this stream yet");
+  DEVICE_GUARD(h->device);
+  HIP_TRY(hipMemsetAsync(cx->arena, byte, cx->arena_bytes, s));
+  return CLASFV_OK;
 }
 
 // ---- diagnostics: one conv / the decoder alone, through the forward's own dispatch ---------------

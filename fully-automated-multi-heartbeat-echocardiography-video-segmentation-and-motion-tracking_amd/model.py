@@ -163,6 +163,11 @@ class Engine:
     def workspace_bytes(self):
         return int(self.lib.clasfv_workspace_bytes(self.h))
 
+    def fill_workspace(self, byte, stream=None):
+        """Fill the whole workspace arena of `stream`'s context with `byte` (clasfv_fill_workspace; tests)."""
+        _lib.check(self.lib.clasfv_fill_workspace(self.h, int(byte), _lib.stream_ptr(stream, self.device)),
+                   "clasfv_fill_workspace")
+
 
 class R2plus1D_18_MotionNet(nn.Module):
     """HIP-backed drop-in for the reference model (inference)."""

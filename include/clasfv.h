@@ -160,6 +160,12 @@ int clasfv_set_launch_log(clasfv_t h, int enable);
  * of entries; CLASFV_EINVAL, with the log kept, when more than cap are waiting. At most 65536 launches
  * are kept between two calls. */
 int clasfv_launch_log(clasfv_t h, int cap, const char** labels, int64_t* grids, int* passes, int* convs);
+/* Fill the whole workspace arena of the context that belongs to `stream` (the buffers clasfv_forward
+ * carves out of it and the slack between them) with `byte`, by hipMemsetAsync on that stream:
+ * stream-ordered, no synchronisation. For tests that a result does not depend on what the arena held
+ * (0xFF in every byte is a NaN in fp32 and in bf16). CLASFV_EINVAL for a null handle, a byte outside
+ * [0, 255], or a stream no clasfv_forward / clasfv_run_decoder has created a context for yet. */
+int clasfv_fill_workspace(clasfv_t h, int byte, void* stream);
 
 /* ---- diagnostics: one layer alone (for layer-level tests; not on the reference's interface) - */
 /* New exports only: the ABI revision is unchanged. Convs are numbered in execution order: the

@@ -10,7 +10,9 @@ Per case:
      the kernel's family (BARS below: 4 x the largest e measured on the MI355X,
      profiles/r07a_layer_errors.txt); bf16 outputs get one bf16 ulp of |y64| on top;
  (c) memory discipline: guard bands around the output and the split-K scratch untouched, every
-     element written, padded output channels exactly +0, `res` aliasing `y` equal to the plain run.
+     element written, padded output channels exactly +0, `res` aliasing `y` equal to the plain run;
+     every input (x, x2, res, the decoder's taps) lies between guard bands of the same NaN pattern, so a
+     value read outside an input fails (a) and (b), and no launch changes an input or its bands.
 """
 import os
 import re
@@ -333,6 +335,19 @@ def guarded(numel, dtype, device):
     return buf, bits, buf[GUARD:GUARD + numel]
 
 
+def guarded_input(t, dev):
+    """A copy of t on dev between two guard bands (guarded()), shaped as t, and the record inputs_intact
+    checks after a launch: the buffer's bits and a snapshot of the payload's."""
+    _, bits, payload = guarded(t.numel(), t.dtype, dev)
+    payload.copy_(t.reshape(-1))
+    return payload.view(t.shape), (bits, bits[GUARD:GUARD + t.numel()].clone())
+
+
+def inputs_intact(records):
+    """No kernel writes its inputs: bands still all ones, payloads as they were handed over."""
+    return all(guards_intact(bits) and torch.equal(bits[GUARD:bits.numel() - GUARD], snap) for bits, snap in records)
+
+
 def on_device(fn):
     """Run fn (launches + synchronise). A HIP error ends the whole session: nothing more is launched on a
     device that has faulted. An argument the engine refuses (CLASFV_EINVAL / EBADSHAPE) is an ordinary error."""
@@ -393,14 +408,19 @@ def build_case(nt, c):
                                            channels=chans)
     dev = nt.engine.device
     xs = [x[:, :e["cin"]], x[:, e["cin"]:]] if e["cin2"] else [x]
-    x_dev = LR.to_channels_last(xs[0], e["cin_p"], e["in_dtype"]).to(dev)
+    x_dev = LR.to_channels_last(xs[0], e["cin_p"], e["in_dtype"])
     if c["x_c8"]:
         x_dev = LR.to_c8(x_dev)
-    x2_dev = LR.to_channels_last(xs[1], e["cin2"], e["in_dtype"]).to(dev) if e["cin2"] else None
-    res_dev = None
+    x_dev, rec = guarded_input(x_dev, dev)
+    records = [rec]
+    x2_dev = res_dev = None
+    if e["cin2"]:
+        x2_dev, rec = guarded_input(LR.to_channels_last(xs[1], e["cin2"], e["in_dtype"]), dev)
+        records.append(rec)
     if res is not None:
-        res_dev = LR.to_channels_last(res, e["cout_p"], e["out_dtype"]).to(dev)
-    return dict(e=e, x=x_dev, x2=x2_dev, res=res_dev, y64=y, den=den, out=(n, to_, ho, wo), chans=chans,
+        res_dev, rec = guarded_input(LR.to_channels_last(res, e["cout_p"], e["out_dtype"]), dev)
+        records.append(rec)
+    return dict(e=e, x=x_dev, x2=x2_dev, res=res_dev, inputs=records, y64=y, den=den, out=(n, to_, ho, wo), chans=chans,
                 xmin=float(x.abs()[x != 0].min()) if x.numel() else 0.0, wfmin=float(wf.abs()[wf != 0].min()))
 
 
@@ -429,6 +449,7 @@ def launch(nt, c, b, relu, alias=False):
     finally:
         nt.engine.set_variants(*old)
     assert name == c["kernel"], f"pick_kernel chose {name}"
+    assert inputs_intact(b["inputs"]), "an input or its guard bands were written"
     assert guards_intact(ybits), "write outside the output tensor"
     assert sbits is None or guards_intact(sbits), "write outside the split-K scratch"
     assert bool((ybits[GUARD:GUARD + numel] != -1).all()), "output elements left unwritten"
@@ -621,10 +642,12 @@ def case_keys():
         to_, ho, wo = (LR.out_dim(d, kk, ss, pp)
                        for d, kk, ss, pp in zip((t, h, w), e["kernel"], e["stride"], e["padding"]))
         m = n * to_ * ho * wo
-        x = torch.zeros(n * t * h * w * e["cin_p"], dtype=e["in_dtype"], device=dev)
-        x2 = torch.zeros(n * t * h * w * e["cin2"], dtype=e["in_dtype"], device=dev) if e["cin2"] else None
+        ins = [torch.zeros(n * t * h * w * e["cin_p"], dtype=e["in_dtype"], device=dev),
+               torch.zeros(n * t * h * w * e["cin2"], dtype=e["in_dtype"], device=dev) if e["cin2"] else None]
         y = torch.zeros(m * e["cout_p"], dtype=e["out_dtype"], device=dev)
-        res = torch.zeros_like(y) if c["res"] else None
+        ins.append(torch.zeros_like(y) if c["res"] else None)
+        (x, x2, res), records = zip(*[guarded_input(a, dev) if a is not None else (None, None) for a in ins])
+        records = [r for r in records if r is not None]
         scratch = None
         if e["kernel"][0] == 3 and ".conv" in c["layer"]:  # as launch(): the block's 3x1x1 convs get split-K scratch
             scratch = torch.zeros(4 * m * e["cout_p"], dtype=torch.float32, device=dev)
@@ -640,6 +663,7 @@ def case_keys():
                 convs = [label_kernel(label) for label, _, _, _ in log if label_kernel(label) != "split_sum_kernel"]
                 assert [REPORTED_AS.get(k, k) for k in convs] == [name], f"{case_id(c)}: log {log}, reported {name}"
                 assert all(conv == e["index"] for _, _, _, conv in log)
+                assert inputs_intact(records), f"{case_id(c)}: an input or its guard bands were written"
                 for key in log_keys(log):
                     keys.setdefault(key, case_id(c))
         finally:
@@ -652,10 +676,12 @@ def case_keys():
         eng.set_launch_log(True)
         try:
             for n, t, h, w in DEC_SHAPES:
-                taps = [torch.zeros((n,) + s + (64,), device=dev) for s in LR.tap_shapes(t, h, w)]
+                taps, records = zip(*[guarded_input(torch.zeros((n,) + s + (64,), device=dev), dev)
+                                      for s in LR.tap_shapes(t, h, w)])
                 seg = torch.empty(n * 2 * t * h * w, device=dev)
                 mot = torch.empty(n * 4 * t * h * w, device=dev)
                 on_device(lambda: (eng.run_decoder(taps, (n, t, h, w), seg, mot), torch.cuda.synchronize()))
+                assert inputs_intact(records), "a decoder tap or its guard bands were written"
                 for key in log_keys(eng.launch_log()):
                     keys.setdefault(key, f"decoder-{dtype}-{'-'.join(flags) or 'product'}-{n}x{t}x{h}x{w}")
         finally:
@@ -742,7 +768,7 @@ def test_decoder_alone_vs_float64_head(nthw, dtype, flags):
     taps = [LR.signed_unit((n, 64) + s, gen, torch.float32) for s in LR.tap_shapes(t, h, w)]
     rs, rm = LR.decoder_reference(nt.sd, [p.double() for p in taps], (t, h, w))
     dev = nt.engine.device
-    taps_dev = [LR.to_channels_last(p, 64, torch.float32).to(dev) for p in taps]
+    taps_dev, records = zip(*[guarded_input(LR.to_channels_last(p, 64, torch.float32), dev) for p in taps])
     _, sbits, seg = guarded(n * 2 * t * h * w, torch.float32, dev)
     _, mbits, mot = guarded(n * 4 * t * h * w, torch.float32, dev)
     old = nt.engine.set_variants(*flags)
@@ -750,6 +776,7 @@ def test_decoder_alone_vs_float64_head(nthw, dtype, flags):
         on_device(lambda: (nt.engine.run_decoder(taps_dev, nthw, seg, mot), torch.cuda.synchronize()))
     finally:
         nt.engine.set_variants(*old)
+    assert inputs_intact(records), "a decoder tap or its guard bands were written"
     assert guards_intact(sbits) and guards_intact(mbits), "write outside seg / motion"
     assert bool((sbits[GUARD:-GUARD] != -1).all()) and bool((mbits[GUARD:-GUARD] != -1).all()), "voxels left unwritten"
     es = float((seg.reshape(n, 2, t, h, w).double().cpu() - rs).abs().max())
@@ -773,7 +800,8 @@ def test_decoder_rejects_partial_tiles(nthw):
     nt = net("fp32", "float")
     n, t, h, w = nthw
     dev = nt.engine.device
-    taps = [torch.zeros((n,) + s + (64,), device=dev) for s in LR.tap_shapes(t, h, w)]
+    taps, records = zip(*[guarded_input(torch.zeros((n,) + s + (64,), device=dev), dev)
+                          for s in LR.tap_shapes(t, h, w)])
     _, sbits, seg = guarded(n * 2 * t * h * w, torch.float32, dev)
     _, mbits, mot = guarded(n * 4 * t * h * w, torch.float32, dev)
     from clasfv_amd import _lib
@@ -781,4 +809,5 @@ def test_decoder_rejects_partial_tiles(nthw):
                                           _lib.ptr(mot), _lib.stream_ptr(None, dev))
     torch.cuda.synchronize()
     assert rc == -2
+    assert inputs_intact(records)
     assert bool((sbits == -1).all()) and bool((mbits == -1).all())

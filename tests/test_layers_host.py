@@ -111,3 +111,12 @@ def test_launch_log_entries_reject_a_null_handle():
     assert lib.clasfv_launch_log(None, 4, labels, grids, passes, convs) == -1
     assert b"null handle" in lib.clasfv_last_error()
     assert lib.clasfv_launch_log(None, 0, None, None, None, None) == -1
+
+
+def test_fill_workspace_rejects_a_null_handle():
+    from clasfv_amd import _lib
+    lib = _lib.load()
+    assert lib.clasfv_param_info(None, 0, None, None, None) == -1  # leaves another message behind
+    assert lib.clasfv_fill_workspace(None, 0xFF, None) == -1
+    assert b"null handle" in lib.clasfv_last_error()
+    assert lib.clasfv_workspace_bytes(None) == 0

@@ -9,7 +9,8 @@ under the float bar.
 
 Per case, on one set of inputs and one float64 reference (tests/test_layers_gpu.py's builders):
  * each kernel under the wino4 family bar of test_layers_gpu (BARS["wino4"]), ReLU off and on, with that
-   file's memory discipline (guard bands, every element written, padded channels +0);
+   file's memory discipline (guard bands around the output and around x, whose whole-line staging must
+   not carry a byte from outside it into a kept output; every element written, padded channels +0);
  * the three outputs bit-equal.
 Integer data (two cases): every kernel's output snapped to the nearest multiple of 1/2 equals the exact
 result, so a channel fetched from the wrong place is an exact mismatch.
