@@ -54,6 +54,7 @@ SIGNATURES = {
     "clasfv_preprocess_video": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "clasfv_track": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
                              c_int, _P, _P]),
+    "clasfv_lv_geometry": (c_int, [_P, c_int64, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
 }
 
 ABI_VERSION = 3  # CLASFV_ABI_VERSION of include/clasfv.h these signatures describe
@@ -63,6 +64,8 @@ FUSE_FORCE_GENERIC = 0x100
 TRACK_BILINEAR, TRACK_NEAREST = 0, 1
 TRACK_FORCE_STEPS, TRACK_FORCE_LDS = 0x100, 0x200
 TRACK_LDS_MAX_PIXELS, TRACK_LDS_AUTO_PIXELS = 20480, 2304
+# CLASFV_LV_* (include/clasfv.h)
+LV_NPUCKS, LV_STRIDE, LV_MAX_PIXELS = 10, 12, 162816
 # CLASFV_VARIANT_* bits (include/clasfv.h)
 VARIANTS = {"no_winograd": 1, "no_wino_patch": 2, "winot_reference": 4, "no_c8": 8, "no_stem_bf16": 16,
             "no_patch_bf16": 32, "no_decoder_bf16": 64, "winot_no_ts1": 128, "no_split_k": 256, "no_wino4": 512,

@@ -17,6 +17,7 @@
 
 #include "clasfv.h"
 #include "common.h"
+#include "lvgeom.h"
 #include "plumbing.h"
 #include "track.h"
 
@@ -1557,6 +1558,19 @@ int clasfv_track(const float* img, int N, int C, int H, int W, const float* moti
   const uint64_t frame = (uint64_t)N * C * H * W * sizeof(float);
   if (i0 < o0 + frame * (uint64_t)P && o0 < i0 + frame) return fail(CLASFV_EINVAL, "out overlaps img");
   HIP_TRY(launch_track(img, N, C, H, W, motion, m_sn, m_sc, m_st, t0, t_step, P, mode, out, (hipStream_t)stream));
+  return CLASFV_OK;
+}
+
+int clasfv_lv_geometry(const uint8_t* masks, int64_t F, int H, int W, int label, double sy, double sx, int32_t* area,
+                       double* geom, void* stream) {
+  if (!masks || !area || !geom) return fail(CLASFV_EINVAL, "bad argument (null pointer)");
+  if (F < 1 || H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad argument (F, H and W must be >= 1)");
+  if (label < 0 || label > 255) return fail(CLASFV_EINVAL, "bad argument (label must be in [0, 255])");
+  if (!(isfinite(sy) && isfinite(sx) && sy > 0.0 && sx > 0.0))
+    return fail(CLASFV_EINVAL, "bad argument (the spacings must be finite and positive)");
+  if ((int64_t)H * W > CLASFV_LV_MAX_PIXELS)
+    return fail(CLASFV_EBADSHAPE, "the frame is kept in LDS: H * W must be <= 162816");
+  HIP_TRY(launch_lv_geometry(masks, F, H, W, label, sy, sx, area, geom, (hipStream_t)stream));
   return CLASFV_OK;
 }
 

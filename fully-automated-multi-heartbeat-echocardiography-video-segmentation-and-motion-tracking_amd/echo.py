@@ -19,6 +19,11 @@ Behaviour (not code) of the reference's EF stage, re-derived from SURVEY.md sect
   eigen-decomposition (one pixel) (0.0, zeros).
 * ``compute_ef_batch``: the same for many videos on a thread pool (numpy / scipy release the GIL in
   their kernels), for the batched multi-video path.
+* ``lv_curve`` / ``ef_from_curve``: the device side. ``lv_curve`` runs get2dPucks and the disk volume of EVERY
+  frame of device masks in one kernel launch (clasfv_lv_geometry, csrc/lvgeom.hip) -- the per-frame volume
+  curve the reference computes for each video it annotates (src/visualization_utils.py:487-493) --
+  and ``ef_from_curve`` is compute_ef_using_putative_clips from such a curve (``ed_es_pairs`` is the frame
+  selection both share). The host functions above stay the parity path.
 
 Pinned by tests/golden/ef.npz, which the reference code itself produced (tests/golden/make_golden_ef.py).
 """
@@ -84,16 +89,22 @@ def _disk_volume(length, radii):
     return np.sum(np.pi * radii * radii * length / len(radii))
 
 
-def compute_ef_using_putative_clips(fused_segmentations, test_pat_index, return_edes=False):
-    seg = np.asarray(fused_segmentations)
-    area = seg.sum(axis=(1, 2)).ravel()
+def ed_es_pairs(area):
+    """[(ED, ES)] frame pairs of a per-frame LV area curve: the peak and percentile selection of
+    compute_ef_using_putative_clips (see the module docstring)."""
     p5, p85, p95 = np.percentile(area, [5, 85, 95])
     prom = 0.50 * (p95 - p5)
     es = find_peaks(-area, distance=20, prominence=prom)[0]
     ed = [int(i) for i in find_peaks(area, distance=20, prominence=prom)[0] if area[i] >= p85]
     if np.mean(area[:3]) >= p85:
         ed.insert(0, 0)
-    pairs = EDESpairs(np.array(ed), es)
+    return EDESpairs(np.array(ed), es)
+
+
+def compute_ef_using_putative_clips(fused_segmentations, test_pat_index, return_edes=False):
+    seg = np.asarray(fused_segmentations)
+    area = seg.sum(axis=(1, 2)).ravel()
+    pairs = ed_es_pairs(area)
     frames = seg.reshape(-1, seg.shape[-2], seg.shape[-1])
     efs = []
     for d, s in pairs:
@@ -114,6 +125,90 @@ def compute_ef_batch(segmentations, names=None, return_edes=False, workers=8):
     with ThreadPoolExecutor(max(1, workers)) as ex:
         return list(ex.map(lambda a: compute_ef_using_putative_clips(a[0], a[1], return_edes),
                            zip(segmentations, names)))
+
+
+class LvCurve:
+    """Per-frame LV geometry of a mask video: ``area`` (int32 pixel count), ``length`` (long axis),
+    ``radii`` (..., 10) and ``volume`` (Simpson's method of disks), float64, over the leading shape of the
+    masks. ``lv_curve`` returns device tensors; ``cpu()`` the same curve as numpy arrays."""
+
+    __slots__ = ("area", "geom")
+
+    def __init__(self, area, geom):
+        self.area, self.geom = area, geom  # geom (..., 12): length, radii[10], volume, as the library writes it
+
+    length = property(lambda self: self.geom[..., 0])
+    radii = property(lambda self: self.geom[..., 1:-1])
+    volume = property(lambda self: self.geom[..., -1])
+
+    def cpu(self):
+        if isinstance(self.area, np.ndarray):
+            return self
+        return LvCurve(self.area.cpu().numpy(), self.geom.cpu().numpy())
+
+    def asdict(self):
+        """{"area", "length", "radii", "volume"}: numpy arrays (what the CLI pickles)."""
+        c = self.cpu()
+        return {k: np.ascontiguousarray(getattr(c, k)) for k in ("area", "length", "radii", "volume")}
+
+
+def lv_curve(masks, label=1, spacing=(1.0, 1.0)):
+    """get2dPucks and the disk volume of every frame, on the device, in one kernel launch
+    (clasfv_lv_geometry; include/clasfv.h states the per-frame rules). ``masks``: a device tensor (F,H,W)
+    or (N,T,H,W) of an integer dtype; a pixel belongs to the structure iff it equals ``label``. uint8 masks
+    are read in place, others (the int64 of warp.track_labels, of the widened masks) are compared with
+    ``label`` on the device first. ``spacing`` = pixel spacing per image axis. Returns an LvCurve of device
+    tensors on the masks' stream. Agrees with the host functions to float64 rounding except on frames where a
+    rim pixel ties with a slab cut ("LV geometry")."""
+    import torch
+    from . import _lib
+    if not torch.is_tensor(masks):
+        raise ValueError("masks must be a tensor on the GPU (the library reads its device pointer)")
+    if masks.is_floating_point() or masks.is_complex():
+        raise ValueError(f"masks of an integer dtype expected, not {masks.dtype}")
+    if masks.dim() not in (3, 4) or masks.numel() == 0:
+        raise ValueError(f"masks (F,H,W) or (N,T,H,W) with at least one frame expected, got {tuple(masks.shape)}")
+    h, w = masks.shape[-2:]
+    if h * w > _lib.LV_MAX_PIXELS:
+        raise ValueError(f"frames of at most {_lib.LV_MAX_PIXELS} pixels are supported, got {h} x {w}")
+    sy, sx = (float(s) for s in spacing)
+    if not (np.isfinite(sy) and np.isfinite(sx) and sy > 0 and sx > 0):
+        raise ValueError(f"spacing must be two finite positive numbers, got {spacing!r}")
+    if masks.dtype == torch.uint8 and (int(label) != label or not 0 <= label <= 255):
+        raise ValueError(f"label {label!r} is not a value of uint8 masks")
+    if not masks.is_cuda:
+        raise ValueError(f"masks must be on the GPU (the library reads their device pointer), not on {masks.device}")
+    if masks.dtype == torch.uint8:
+        frames, lab = masks.contiguous(), int(label)
+    else:
+        # the comparison keeps a permuted input's strides; the library reads a dense (F,H,W) block
+        frames, lab = (masks == label).to(torch.uint8).contiguous(), 1
+    lead = tuple(masks.shape[:-2])
+    area = torch.empty(lead, device=masks.device, dtype=torch.int32)
+    geom = torch.empty(lead + (_lib.LV_STRIDE,), device=masks.device, dtype=torch.float64)
+    lib = _lib.load()
+    _lib.check(lib.clasfv_lv_geometry(_lib.ptr(frames), area.numel(), h, w, lab, sy, sx, _lib.ptr(area), _lib.ptr(geom),
+                                      _lib.stream_ptr(device=masks.device)), "clasfv_lv_geometry")
+    return LvCurve(area, geom)
+
+
+def ef_from_curve(area, volume, name, return_edes=False):
+    """compute_ef_using_putative_clips from a per-frame curve (LvCurve.area, LvCurve.volume of one video;
+    arrays or tensors): the same ED / ES pairs, EF = (V[ED] - V[ES]) / V[ED] * 100, negative EFs reported
+    and dropped."""
+    area, volume = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (area, volume))
+    if area.ndim != 1 or area.shape != volume.shape:
+        raise ValueError(f"area and volume of one video (T,) expected, got {area.shape} and {volume.shape}")
+    pairs = ed_es_pairs(area)
+    efs = []
+    for d, s in pairs:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ef = (volume[d] - volume[s]) / volume[d] * 100
+        if ef < 0:
+            print("Negative EF at patient: " + str(name))
+            continue
+        efs.append(ef)
+    return (efs, pairs) if return_edes else efs
 
 
 def categorical_dice(prediction, truth, k, epsilon=1e-5):

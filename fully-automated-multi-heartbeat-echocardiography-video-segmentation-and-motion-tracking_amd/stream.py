@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import fuse_utils as FU
+from .echo import LvCurve, lv_curve
 from .preprocess import preprocess_video
 
 
@@ -81,7 +82,10 @@ class VideoStream:
             self._ring_ev[slot] = ev
         return dev, ev, (host if slot is None else None)
 
-    def run(self, frame_videos, return_device=False):
+    def run(self, frame_videos, return_device=False, curves=False):
+        """``curves=True``: each video's LV curve (echo.lv_curve of its fused masks: per-frame area, length,
+        radii, volume) is computed on the video's lane stream right after fusion and comes back with the
+        masks in the same pinned transfer; every result is then ``(masks, curve)``."""
         videos = list(frame_videos)
         if not videos:
             return []
@@ -89,7 +93,7 @@ class VideoStream:
         lanes = [compute] + self.lanes
         for ls in self.lanes:
             ls.wait_stream(compute)
-        outs, keep, host_out = [], [], []
+        outs, keep, host_out, lvs = [], [], [], []
         pending = self._upload(videos[0])
         for i in range(len(videos)):
             dev, ev, pinned_src = pending
@@ -101,8 +105,13 @@ class VideoStream:
             with torch.cuda.stream(cs):
                 video = preprocess_video(dev, self.height, self.width, device=self.device)
                 fused = FU.segment_a_video_with_fusion_device(video, self.model, **self.kw)
+                if curves:
+                    lvs.append(lv_curve(fused))
             if cs is not compute:
                 fused.record_stream(compute)  # read by the caller's stream (D2H copies, return_device)
+                if curves:
+                    lvs[-1].area.record_stream(compute)
+                    lvs[-1].geom.record_stream(compute)
             if return_device:
                 outs.append(fused)
             else:
@@ -115,9 +124,13 @@ class VideoStream:
         if return_device:
             compute.synchronize()
             self.copy_stream.synchronize()
-            return outs
+            return list(zip(outs, lvs)) if curves else outs
         # one pinned buffer for every mask of the call, filled by async D2H copies on the compute stream
         total = sum(int(np.prod(sh)) for sh in host_out)
+        if curves:  # the curves follow the masks in the same buffer: all float64 blocks, then all int32 areas
+            geom_at = -(-total // 8) * 8
+            area_at = geom_at + sum(c.geom.numel() for c in lvs) * 8
+            total = area_at + sum(c.area.numel() for c in lvs) * 4
         flat = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
         res, at = [], 0
         for fused in outs:
@@ -126,13 +139,25 @@ class VideoStream:
             dst.copy_(fused, non_blocking=True)
             res.append(dst)
             at += n
+        host_lvs = []
+        for c in (lvs if curves else ()):
+            geom = flat[geom_at:geom_at + c.geom.numel() * 8].view(torch.float64).view(c.geom.shape)
+            area = flat[area_at:area_at + c.area.numel() * 4].view(torch.int32).view(c.area.shape)
+            geom.copy_(c.geom, non_blocking=True)
+            area.copy_(c.area, non_blocking=True)
+            host_lvs.append((area, geom))
+            geom_at += c.geom.numel() * 8
+            area_at += c.area.numel() * 4
         compute.synchronize()
         self.copy_stream.synchronize()
-        return [r.numpy().astype(np.int64) for r in res]
+        masks = [r.numpy().astype(np.int64) for r in res]
+        if curves:
+            return [(m, LvCurve(a.numpy().copy(), g.numpy().copy())) for m, (a, g) in zip(masks, host_lvs)]
+        return masks
 
 
 def segment_videos(frame_videos, model, num_clips=5, step=1, fuse_method="simple", height=112, width=112,
-                   batch_size=None, strict_reference=True):
-    """Convenience wrapper: VideoStream(...).run(frame_videos)."""
+                   batch_size=None, strict_reference=True, curves=False):
+    """Convenience wrapper: VideoStream(...).run(frame_videos, curves=curves)."""
     return VideoStream(model, num_clips, step, fuse_method, height, width, batch_size,
-                       strict_reference=strict_reference).run(frame_videos)
+                       strict_reference=strict_reference).run(frame_videos, curves=curves)

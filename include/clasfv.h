@@ -277,6 +277,34 @@ int clasfv_track(const float* img_dev, int N, int C, int H, int W, const float* 
                  int64_t m_sc, int64_t m_st, int T, int t0, int t_step, int P, int mode, float* out_dev,
                  void* stream);
 
+/* ---- LV geometry (src/utils/echo_utils.py:259-385, src/visualization_utils.py:487-493) ----------- */
+/* Area, long-axis length, the ten disk radii and the Simpson volume of every frame of masks_dev (F,H,W)
+ * uint8, in ONE launch (one workgroup per frame, the frame in LDS): get2dPucks(frame == label, (sy, sx))
+ * and computeSimpsonVolume of the reference, per frame, in float64. A pixel belongs to the structure iff it
+ * equals `label` (so ITK voting's undecided label 2 is background for label 1). area_dev[f] is the pixel
+ * count; geom_dev[f * CLASFV_LV_STRIDE ..] holds length, radii[0..9], volume.
+ * Per frame, with coordinates (i * sy, j * sx) over the n member pixels: n = 0 gives (1, zeros, 0) and
+ * n = 1 gives (0, zeros, 0). Otherwise the axes are the eigenvectors of the sample covariance (divisor
+ * n - 1), larger eigenvalue first; an exactly diagonal covariance yields the coordinate axes, i first only
+ * when var_i > var_j; each axis k is negated when its own k-th component is negative. The rim is every pixel
+ * whose 4-neighbourhood, frame edges replicated, is mixed; each rim pixel less the mean member coordinate is
+ * projected onto (major, minor); lo, hi = min, max along the major axis, length = hi - lo; cut k =
+ * lo + k * (hi - lo) / 10 and cut 10 = hi; a rim pixel is in slab k iff cut k <= x < cut k + 1 (the pixel
+ * attaining hi is in none, as in the reference); radius k = median of |minor| over slab k (mean of the two
+ * middle values for an even count, NaN for an empty slab); volume = sum pi * r^2 * length / 10 (NaN when a
+ * radius is). A frame without rim (every pixel a member) gives NaN length, radii and volume.
+ * The moments are exact integers and min, max and medians exact selections, so a frame's results do not
+ * depend on F or on its place in the batch; they agree with the host functions to float64 rounding except
+ * where a rim pixel ties with a cut ("LV geometry"). Any rim count up to H * W is served.
+ * Stream-ordered; no handle, no workspace; masks_dev needs no alignment. CLASFV_EINVAL, before any HIP
+ * call, for a null pointer, F < 1, H or W < 1, label outside [0, 255] or a spacing that is not finite and
+ * positive; CLASFV_EBADSHAPE for H * W > CLASFV_LV_MAX_PIXELS. */
+#define CLASFV_LV_NPUCKS 10
+#define CLASFV_LV_STRIDE 12         /* doubles per frame: length, radii[10], volume */
+#define CLASFV_LV_MAX_PIXELS 162816 /* as SIMPLE fusion: one frame's bytes beside the kernel's LDS state */
+int clasfv_lv_geometry(const uint8_t* masks_dev, int64_t F, int H, int W, int label, double sy, double sx,
+                       int32_t* area_dev, double* geom_dev, void* stream);
+
 /* ---- preprocessing (motion_segment.py:96-106, src/echonet_dataset.py:38-50) --------------------- */
 /* frames_dev (T,Hs,Ws,3) uint8 RGB -> out_dev (3,T,H,W) float32, resized as
  * F.interpolate(size=(T,H,W), mode="trilinear", align_corners=True) on the (1,3,T,Hs,Ws) float

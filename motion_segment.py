@@ -36,7 +36,8 @@ def parse_args(argv=None):
     ap.add_argument("-o", "--output", required=False, type=str, help="Path to the output files", default=".")
     ap.add_argument("-v", "--verbose", action="store_true", help="Verbosity")
     ap.add_argument("-c", "--content", required=False, type=str,
-                    help="Content of the output: gif, binary, binary_video, all", default="binary")
+                    help="Content of the output: gif, binary, binary_video, all; also volume_curve (not part of "
+                         "all): the per-frame LV area, length, radii and volume", default="binary")
     ap.add_argument("--height", required=False, type=int, help="Height of image (pretrain model uses 112)", default=112)
     ap.add_argument("--width", required=False, type=int, help="Width of image (pretrain model uses 112)", default=112)
     ap.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED",
@@ -91,8 +92,8 @@ def main(argv=None):
             dev = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(dev)
 
-    from clasfv_amd.echo import compute_ef_using_putative_clips
-    from clasfv_amd.fuse_utils import segment_a_video_with_fusion
+    from clasfv_amd.echo import compute_ef_using_putative_clips, lv_curve
+    from clasfv_amd.fuse_utils import segment_a_video_with_fusion_device
     from clasfv_amd.model import R2plus1D_18_MotionNet
     from clasfv_amd.preprocess import preprocess_video
     from clasfv_amd.weights import DEFAULT_SEED, load_checkpoint
@@ -108,10 +109,11 @@ def main(argv=None):
     # motion_segment.py:96-106 on the device: uint8 frames -> resize -> zero-one normalisation
     video = preprocess_video(read_video(args.path), args.height, args.width, device=dev)
 
-    segmentations = segment_a_video_with_fusion(video, model=model, interpolate_last=True, step=args.step,
-                                                num_clips=args.fuse, fuse_method=args.fuse_method, class_list=[0, 1],
-                                                batch_size=args.batch_size,
-                                                strict_reference=not args.no_strict_reference)
+    fused = segment_a_video_with_fusion_device(video, model=model, interpolate_last=True, step=args.step,
+                                               num_clips=args.fuse, fuse_method=args.fuse_method, class_list=[0, 1],
+                                               batch_size=args.batch_size,
+                                               strict_reference=not args.no_strict_reference)
+    segmentations = fused.to(torch.int64).cpu().numpy()  # what segment_a_video_with_fusion returns
     predicted_efs, edes_pairs = compute_ef_using_putative_clips(segmentations, test_pat_index=args.path,
                                                                 return_edes=True)
     if args.verbose:
@@ -138,6 +140,9 @@ def main(argv=None):
     if "binary_video" in content or "all" in content:
         with open(os.path.join(args.output, filename + "_whole_video_segmentation.pkl"), "wb") as f:
             pickle.dump(segmentations, f)
+    if "volume_curve" in content:  # from the device masks, in one kernel launch (echo.lv_curve)
+        with open(os.path.join(args.output, filename + "_lv_volume_curve.pkl"), "wb") as f:
+            pickle.dump(lv_curve(fused).asdict(), f)
     return segmentations, predicted_efs, edes_pairs
 
 
