@@ -23,6 +23,8 @@ SIGNATURES = {
     "clasfv_finalize": (c_int, [_P]),
     "clasfv_forward": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "clasfv_workspace_bytes": (c_int64, [_P]),
+    "clasfv_max_clips": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "clasfv_clips_fit": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "clasfv_set_compute_dtype": (c_int, [_P, c_int]),
     "clasfv_get_compute_dtype": (c_int, [_P]),
     "clasfv_set_kernel_variants": (c_int, [_P, c_int]),

@@ -211,6 +211,8 @@ hipError_t launch_twalk_bf16(const ConvParams& p, hipStream_t s);
 bool stem_bf16_supported(const ConvParams& p);
 hipError_t launch_stem_bf16(const ConvParams& p, hipStream_t s);
 hipError_t launch_decoder(const DecParams& p, hipStream_t s);
+// Every tap below 2^31 floats and the grid below 2^31 blocks (reads the sizes of p only).
+bool decoder_addressable(const DecParams& p);
 constexpr int DECODER_X3_ELEMS = 3 * 4096 + 3 * 1024;  // bf16 values of DecParams::w2x3
 void decoder_x3_weights(const float* w2, const float* wh, uint16_t* out);
 hipError_t launch_pack_input(const float* x, float* y, int N, int T, int HW, hipStream_t s);

@@ -628,13 +628,20 @@ __global__ __launch_bounds__(32 * TROWS) __attribute__((amdgpu_waves_per_eu(((MO
 
 }  // namespace
 
+// The sizes the decoder addresses (sizes only: pointers and weights of p are not read): the staging loads
+// form 32-bit signed element offsets into every tap, and the grid (one block per 8-row tile, the product
+// form) is an int. The engine asks before its first launch; launch_dec asks again.
+bool decoder_addressable(const DecParams& p) {
+  for (int i = 0; i < 4; ++i)
+    if ((size_t)p.N * p.tap[i].T * p.tap[i].H * p.tap[i].W * 64 >= ((size_t)1 << 31)) return false;
+  return (size_t)((p.H + 7) / 8) * ((p.W + TILE_W - 1) / TILE_W) * p.T * p.N < ((size_t)1 << 31);
+}
+
 static hipError_t launch_dec(const DecParams& p, hipStream_t s, int mode, int th = 8) {
   if (p.tap[0].T != p.T) return hipErrorInvalidValue;  // tap 0 is staged as a single frame
-  for (int i = 0; i < 4; ++i)  // the staging loads use 32-bit element offsets
-    if ((size_t)p.N * p.tap[i].T * p.tap[i].H * p.tap[i].W * 64 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+  if (!decoder_addressable(p)) return hipErrorInvalidValue;
   if (p.H % th || p.W % TILE_W) return hipErrorInvalidValue;
   const size_t nb = (size_t)(p.H / th) * (p.W / TILE_W) * p.T * p.N;
-  if (nb >= ((size_t)1 << 31)) return hipErrorInvalidValue;
   static_assert(DecGeo<16>::STAGE_FLOATS * 4 <= 64 * 1024, "default dynamic LDS limit");
   const size_t lds = (size_t)(th == 16 ? DecGeo<16>::STAGE_FLOATS : DecGeo<8>::STAGE_FLOATS) * 4;
   void (*k)(DecParams) = nullptr;

@@ -11,6 +11,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <array>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -117,6 +120,38 @@ bool use_wino(const Conv& c, bool bf16, int vflags) {
   if (vflags & CLASFV_VARIANT_NO_WINOGRAD) return false;
   return !bf16 && (c.role == SP1 || c.role == SP2) && c.kt == 1 && c.kh == 3 && c.kw == 3 && c.sh == 1 &&
          c.sw == 1 && c.cin_p % 16 == 0 && c.cout_p % 48 == 0;
+}
+
+// The weight images clasfv_finalize uploads for a conv (after layout_conv) beside Conv::dw, for an engine
+// of this compute dtype and these variants: the upload functions ask here, and so does mark_images, so
+// pick_kernel sees the same images on a finalized handle and on max_clips' device-less plan.
+struct Images {
+  bool x3, wino, wino4, wino4w, wino4r, winot, ws16;
+};
+Images images_of(const Conv& c, bool bf16, int vflags) {
+  Images m{};
+  m.x3 = !c.in_bf16 && !c.stem && c.Kp % 16 == 0;  // conv_dma_x3's split image of the same weights
+  m.wino = use_wino(c, bf16, vflags);
+  m.wino4 = m.wino && c.cout_p % 48 == 0 && c.cin_p % 8 == 0;
+  m.wino4w = m.wino && c.cin_p % 8 == 0 && wino4w_weight_floats(c.cin_p, c.cout_p);
+  m.wino4r = m.wino && c.cin_p % 8 == 0 && wino4r_weight_floats(c.cin_p, c.cout_p);
+  m.winot = use_winot(c, bf16, vflags);
+  // conv_stem_x3's pieces (fp32 engines, 48 channels) / conv_stem_bf16's (bf16 engines, 64)
+  m.ws16 = c.stem && c.kh == 7 && c.kw == 7 && c.cin <= 4 && (bf16 ? c.cout_p == 64 : c.cout_p == 48);
+  return m;
+}
+// Marks the images of images_of (and Conv::dw) present without a device: pointers that are never read.
+void mark_images(Conv& c, bool bf16, int vflags) {
+  const Images m = images_of(c, bf16, vflags);
+  void* const some = &c;
+  c.dw = some;
+  c.dx3 = m.x3 ? some : nullptr;
+  c.dwino = m.wino ? some : nullptr;
+  c.dwino4 = m.wino4 ? some : nullptr;
+  c.dwino4w = m.wino4w ? some : nullptr;
+  c.dwino4r = m.wino4r ? some : nullptr;
+  c.dwinot = m.winot ? some : nullptr;
+  c.dws16 = m.ws16 ? some : nullptr;
 }
 
 // Every CLASFV_VARIANT_* bit of include/clasfv.h with the environment variable that sets it: a switch
@@ -238,6 +273,9 @@ struct clasfv_engine {
   };
   std::vector<Ctx*> ctxs;
   uint64_t ctx_clock = 0;
+  // (T, H, W) -> the largest batch one pass of the network can address (max_clips), for the handle's
+  // finalized state: emptied by whatever changes a kernel choice (finalize, dtype, variants)
+  std::map<std::array<int, 3>, int> clip_limit;
   // per-kernel HIP-event timing of clasfv_forward (clasfv_set_kernel_timing)
   bool ktime = false;
   std::vector<hipEvent_t> evs;  // event pool; evs[0..nev) recorded since the last read
@@ -376,7 +414,7 @@ int upload_conv(Conv& c, F wsrc, const std::vector<double>& scale, const std::ve
         w[(size_t)o * c.Kp + (size_t)tap * c.cin_p + ci] = (float)((double)wsrc(o, ci, tap) * scale[o]);
   int rc = c.in_bf16 ? upload_bf16(w, &c.dw) : upload(w, &c.dw);
   if (rc) return rc;
-  if (!c.in_bf16 && !c.stem && c.Kp % 16 == 0) {  // conv_dma_x3's split image of the same weights
+  if (images_of(c, false, 0).x3) {  // conv_dma_x3's split image of the same weights
     std::vector<uint16_t> x3(dma_x3_weight_elems(c.cout_alloc, c.Kp));
     dma_x3_weight_image(w.data(), c.cout_alloc, c.Kp, x3.data());
     HIP_TRY(hipMalloc(&c.dx3, x3.size() * sizeof(uint16_t)));
@@ -407,17 +445,18 @@ int upload_wino_images(Conv& c, const std::vector<float>& w, const std::vector<d
   std::vector<float> u((size_t)16 * c.cin_p * c.cout_p);
   wino_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u.data());
   if ((rc = upload(u, &c.dwino))) return rc;
-  if (c.cout_p % 48 == 0 && c.cin_p % 8 == 0) {
+  const Images m = images_of(c, false, 0);  // (called for a use_wino conv: the widths decide the rest)
+  if (m.wino4) {
     std::vector<float> u4(wino4_weight_floats(c.cin_p, c.cout_p));
     wino4_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u4.data());
     if ((rc = upload(u4, &c.dwino4))) return rc;
   }
-  if (c.cin_p % 8 == 0 && wino4w_weight_floats(c.cin_p, c.cout_p)) {
+  if (m.wino4w) {
     std::vector<float> uw(wino4w_weight_floats(c.cin_p, c.cout_p));
     wino4w_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, uw.data());
     if ((rc = upload(uw, &c.dwino4w))) return rc;
   }
-  if (c.cin_p % 8 == 0 && wino4r_weight_floats(c.cin_p, c.cout_p)) {
+  if (m.wino4r) {
     std::vector<float> ur(wino4r_weight_floats(c.cin_p, c.cout_p));
     wino4r_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, ur.data());
     if ((rc = upload(ur, &c.dwino4r))) return rc;
@@ -446,8 +485,8 @@ void for_stem_taps(const Conv& c, const std::vector<float>& w, const std::vector
 
 // The stem's split-bf16 images (Conv::dws16); each kernel's pieces keep their own rounding.
 int upload_stem_images(Conv& c, const std::vector<float>& w, const std::vector<double>& s, bool bf16) {
-  if (!c.stem || c.kh != 7 || c.kw != 7 || c.cin > 4) return CLASFV_OK;
-  if (!bf16 && c.cout_p == 48) {  // conv_stem_x3's pieces
+  if (!images_of(c, bf16, 0).ws16) return CLASFV_OK;
+  if (!bf16) {  // conv_stem_x3's pieces
     const size_t img = (size_t)48 * 7 * 8 * 4;
     std::vector<float> ws(3 * img, 0.f);  // hi, mid, lo: bf16 of the remainder, in double
     for_stem_taps(c, w, s, [&](size_t k, float wv, double scale) {
@@ -462,7 +501,7 @@ int upload_stem_images(Conv& c, const std::vector<float>& w, const std::vector<d
     });
     return upload_bf16(ws, &c.dws16);
   }
-  if (bf16 && c.cout_p == 64) {  // conv_stem_bf16's K order
+  {  // conv_stem_bf16's K order
     const size_t img = (size_t)64 * 7 * 8 * 4;
     std::vector<float> ws(2 * img, 0.f);  // hi image, then lo = bf16(w - hi)
     for_stem_taps(c, w, s, [&](size_t k, float wv, double scale) {
@@ -488,9 +527,10 @@ int finalize_conv(clasfv_engine* h, Conv& c, bool bf16) {
   const int cin = c.cin;
   int rc = upload_conv(
       c, [&](int o, int ci, int tap) { return w[((size_t)o * cin + ci) * taps + tap]; }, s, t, true);
-  if (!rc && use_wino(c, bf16, h->tune.vflags)) rc = upload_wino_images(c, w, s);
+  const Images m = images_of(c, bf16, h->tune.vflags);
+  if (!rc && m.wino) rc = upload_wino_images(c, w, s);
   if (!rc) rc = upload_stem_images(c, w, s, bf16);
-  if (!rc && use_winot(c, bf16, h->tune.vflags)) rc = upload_winot_image(c, w, s);
+  if (!rc && m.winot) rc = upload_winot_image(c, w, s);
   return rc;
 }
 
@@ -569,6 +609,7 @@ int finalize_decoder(clasfv_engine* h) {
 struct Shape5 {
   int n, t, h, w, c;
   size_t numel() const { return (size_t)n * t * h * w * c; }
+  int64_t voxels() const { return (int64_t)n * t * h * w; }
 };
 
 // Algorithmic FLOPs of one conv (2 per MAC over the unpadded channels).
@@ -694,7 +735,8 @@ ConvParams conv_params(const Conv& c, const Shape5& in, Shape5& out) {
   p.To = out.t, p.Ho = out.h, p.Wo = out.w, p.Cout = out.c;
   p.KT = c.kt, p.KH = c.kh, p.KW = c.kw, p.st = c.st, p.sh = c.sh, p.sw = c.sw, p.pt = c.pt, p.ph = c.ph, p.pw = c.pw;
   p.K = c.K, p.Kp = c.Kp;
-  p.M = out.n * out.t * out.h * out.w;
+  // (an M past int is clamped, not wrapped: conv_size_error refuses it before anything reads p.M)
+  p.M = (int)std::min<int64_t>(out.voxels(), INT32_MAX);
   p.Cin2 = c.cin2;
   p.stem = c.stem;
   p.in_bf16 = c.in_bf16;
@@ -758,10 +800,45 @@ void split_k(ConvParams& p, int S, void* scratch, size_t scratch_bytes) {
   }
 }
 
-// Runs c on the kernel pick_kernel chooses; *kernel is its kKernels row once chosen.
+// ---- size limits ("Size limits") ---------------------------------------------------------
+// Every *_supported gate implies the addressing assumptions of its own kernel. What no gate can say is
+// checked here before any launch (k: the kernel of one clip of the shape, kn: the kernel pick_kernel
+// gives the whole batch): nullptr when every address the launch forms is in range, else the reason.
+//  * M and the input's voxel count are ints in ConvParams, the FastDiv decodes and every grid.
+//  * The kernel is the one a single clip of the shape runs on. The size clauses of the gates would
+//    otherwise hand a large batch to the next kernel of pick_kernel's list, often one of another rounding
+//    family (F(4x4) -> F(2x2) -> conv_dma_x3), and a clip's bits would depend on its batch.
+//    (launch_winot's conv_winot5 -> conv_winot, the buffer -> pointer forms of conv_dma / conv_dma_x3 and
+//    conv_dma_w -> conv_dma, whose buffer DMAs end at 2^31 bytes, are switches between bit-identical
+//    forms of one kernel, and stay: k is the batch's kernel then.)
+//  * gemm_size_error, once split-K is decided -- the implicit GEMMs (the list's last resort, so nothing
+//    catches what they cannot address): their pointer forms offset x and x2 by 32-bit element counts,
+//    and their grid is an int.
+const char* conv_size_error(Kernel k, Kernel kn, const Shape5& in, const Shape5& out) {
+  constexpr int64_t k31 = (int64_t)1 << 31;
+  if (out.voxels() >= k31) return "the output has 2^31 voxels or more";
+  if (in.voxels() >= k31) return "the input has 2^31 voxels or more";
+  if (kn != k && !(k == K_DMA_W && kn == K_DMA))
+    return "the batch is past the size limit of the kernel one clip of this shape runs on";
+  return nullptr;
+}
+const char* gemm_size_error(const KernelInfo& k, const ConvParams& p, const Shape5& in, const Shape5& out) {
+  constexpr int64_t k31 = (int64_t)1 << 31, k32 = (int64_t)1 << 32;
+  if (k.id == K_DMA_X3 || k.id == K_DMA_W || k.id == K_DMA || k.id == K_STEM_F32) {
+    if (in.voxels() * p.Cin >= k32 || (p.x2 && in.voxels() * p.Cin2 >= k32))
+      return "an input of the implicit GEMM has 2^32 elements or more";
+    // 128-row M tiles, N tiles of >= 16 channels, n_split K ranges
+    if ((out.voxels() / 128 + 1) * (p.Cout / 16 + 1) * (p.n_split > 1 ? p.n_split : 1) >= k31)
+      return "the implicit GEMM's grid has 2^31 blocks or more";
+  }
+  return nullptr;
+}
+
+// Runs c on the kernel pick_kernel chooses; *kernel is its kKernels row once chosen. A shape that kernel
+// cannot address is refused (CLASFV_EBADSHAPE) before anything is launched; dry: stop after that check.
 int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
              hipStream_t s, const void* zero_block, const void* x2, const KernelInfo** kernel, const Tuning& tu,
-             int x_c8 = 0, int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0) {
+             int x_c8 = 0, int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0, bool dry = false) {
   if (in.c != c.cin_p) return fail(CLASFV_EINVAL, "internal: channel mismatch");
   ConvParams p = conv_params(c, in, out);
   p.vflags = tu.vflags;
@@ -774,11 +851,37 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
   p.x2 = x2;
   p.x_c8 = x_c8;
   p.y_c8 = y_c8;
-  const KernelInfo& k = kKernels[pick_kernel(c, p)];
+  // the kernel of one clip of the shape, whatever the batch (conv_size_error)
+  ConvParams p1 = p;
+  p1.N = 1;
+  p1.M = (int)(out.voxels() / out.n);
+  const KernelInfo& k1 = kKernels[pick_kernel(c, p1)];
+  const Kernel kn = pick_kernel(c, p);
+  *kernel = &k1;
+  if (const char* why = conv_size_error(k1.id, kn, in, out))
+    return fail(CLASFV_EBADSHAPE, std::string(k1.name) + ": " + why + " (N=" + std::to_string(in.n) + " T=" +
+                                      std::to_string(in.t) + " H=" + std::to_string(in.h) + " W=" + std::to_string(in.w) +
+                                      " C=" + std::to_string(in.c) + ")");
+  const KernelInfo& k = kKernels[kn];  // k1, or conv_dma for conv_dma_w
   *kernel = &k;
   if ((y_c8 && !k.writes_c8) || (x_c8 && !k.reads_c8))
     return fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
+  if (x_c8 && k.id == K_WINOT && !winot_c8_ok(p))  // only launch_winot's conv_winot5 form reads the layout
+    return winot_c8_ok(p1) ? fail(CLASFV_EBADSHAPE, "conv_winot: the 8-channel-blocked input has 2^32 bytes or more")
+                           : fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
   p.w = c.*k.image;
+  int mt = 2, bn = 0;  // the implicit GEMMs' tile
+  if (k.id == K_WINOT) {
+    // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
+    split_k(p, winot_split_for(p), scratch, scratch_bytes);
+  } else if (k.id == K_DMA_X3) {
+    split_k(p, dma_split_for(p, 2), scratch, scratch_bytes);
+  } else if (k.id == K_DMA_W || k.id == K_DMA) {
+    conv_pick_tile(p.M, c.cout_p, tu.conv_nt, &mt, &bn);
+    split_k(p, dma_split_for(p, mt), scratch, scratch_bytes);
+  }
+  if (const char* why = gemm_size_error(k, p, in, out)) return fail(CLASFV_EBADSHAPE, std::string(k.name) + ": " + why);
+  if (dry) return CLASFV_OK;
   switch (k.id) {  // no default: a Kernel without a launch is a compiler warning
     case K_WINO4R: HIP_TRY(launch_wino4r(p, s)); break;
     case K_WINO4W: HIP_TRY(launch_wino4w(p, s)); break;
@@ -787,31 +890,17 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
     case K_WINO: HIP_TRY(launch_wino(p, s)); break;
     case K_STEM_BF16: HIP_TRY(launch_stem_bf16(p, s)); break;
     case K_STEM_X3: HIP_TRY(launch_stem_x3(p, s)); break;
-    case K_WINOT:
-      // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
-      split_k(p, winot_split_for(p), scratch, scratch_bytes);
-      HIP_TRY(launch_winot(p, s));
-      break;
+    case K_WINOT: HIP_TRY(launch_winot(p, s)); break;
     case K_PATCH_BF16: HIP_TRY(launch_patch_bf16(p, s)); break;
     case K_PATCH32_BF16: HIP_TRY(launch_patch32_bf16(p, s)); break;
     case K_TWALK_BF16: HIP_TRY(launch_twalk_bf16(p, s)); break;
     case K_PROJ_X3: HIP_TRY(launch_proj_x3(p, s)); break;
-    case K_DMA_X3:
-      split_k(p, dma_split_for(p, 2), scratch, scratch_bytes);
-      HIP_TRY(launch_dma_x3(p, dma_x3_bn(c.cout_p), s));
-      break;
+    case K_DMA_X3: HIP_TRY(launch_dma_x3(p, dma_x3_bn(c.cout_p), s)); break;
     case K_STEM_F32:  // one N tile (48 fp32 / 64 bf16 channels)
       HIP_TRY(launch_conv(p, 2, c.cout_p, s));
       break;
     case K_DMA_W:
-    case K_DMA: {
-      int mt, bn;
-      conv_pick_tile(p.M, c.cout_p, tu.conv_nt, &mt, &bn);
-      // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
-      split_k(p, dma_split_for(p, mt), scratch, scratch_bytes);
-      HIP_TRY(launch_conv(p, mt, bn, s));
-      break;
-    }
+    case K_DMA: HIP_TRY(launch_conv(p, mt, bn, s)); break;
   }
   return CLASFV_OK;
 }
@@ -1015,6 +1104,128 @@ void log_end(clasfv_engine* h, int conv) {
   }
 }
 
+// The network's launches over n clips of (T, H, W), in forward order, on a workspace laid out by L at
+// `arena`: pack(xin) packs the input, run(...) and run_side(...) run one conv (the latter a decoder
+// projection that may overlap layer4 until join()), decode(taps, shapes, idx) runs the decoder. Each
+// returns a CLASFV code, and the first failure ends the walk. clasfv_forward launches through it;
+// max_clips walks it with runners that only ask whether every launch is inside its kernel's limits.
+template <class Pack, class Run, class RunSide, class Join, class Decode>
+int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, int T, int H, int W, Pack pack, Run run_,
+                 RunSide run_side, Join join, Decode decode) {
+  auto buf = [&](int b) { return reinterpret_cast<void*>(arena + L.off[b]); };
+  // scratch for a temporal conv reading MID: the rest of MID past its input
+  const size_t mid_bytes = L.off[MID + 1] - L.off[MID];
+  auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
+                 const void* x2 = nullptr, int x_c8 = 0, int y_c8 = 0) {
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    if (xin == buf(MID)) {
+      const size_t used = ((size_t)in.n * in.t * in.h * in.w * in.c * sizeof(float) + 255) / 256 * 256;
+      if (used < mid_bytes) {
+        scratch = arena + L.off[MID] + used;
+        scratch_bytes = mid_bytes - used;
+      }
+    }
+    return run_(c, xin, in, y, out, res, relu, x2, x_c8, y_c8, scratch, scratch_bytes);
+  };
+  int rc;
+  if ((rc = pack(buf(XIN)))) return rc;
+  Shape5 sx{N, T, H, W, 4}, s0, sx0;
+  Shape5 sp, sp2, sp3, sp4;  // decoder tap projections
+  size_t ci = 0;
+  // Conv2Plus1D mid tensors (and the stem's) are 8-channel-blocked where c8_pair allows
+  const int c8s = c8_pair(h->convs[0], h->convs[1], sx, h->tune);
+  if ((rc = run(h->convs[ci++], buf(XIN), sx, buf(S0), s0, nullptr, true, nullptr, 0, c8s))) return rc;
+  if ((rc = run(h->convs[ci++], buf(S0), s0, buf(X0), sx0, nullptr, true, nullptr, c8s, 0))) return rc;
+  const int outs[4][2] = {{L1A, L1}, {L2A, L2}, {L3A, L3}, {L4A, L4}};
+  void* cur = buf(X0);
+  Shape5 cs = sx0, taps_shape[5];
+  void* taps[5];
+  taps[0] = cur;
+  taps_shape[0] = cs;
+  for (int li = 0; li < 4; ++li) {
+    for (int b = 0; b < 2; ++b) {
+      const Conv& sp1 = h->convs[ci++];
+      const Conv& tp1 = h->convs[ci++];
+      const Conv& sp2 = h->convs[ci++];
+      const Conv& tp2 = h->convs[ci++];
+      const Conv* ds = (ci < h->convs.size() && h->convs[ci].role == DS) ? &h->convs[ci++] : nullptr;
+      Shape5 sm, sa, sm2, so, sd;
+      const int c8a = c8_pair(sp1, tp1, cs, h->tune);
+      if ((rc = run(sp1, cur, cs, buf(MID), sm, nullptr, true, nullptr, 0, c8a))) return rc;
+      if ((rc = run(tp1, buf(MID), sm, buf(TA), sa, nullptr, true, nullptr, c8a, 0))) return rc;
+      const int c8b = c8_pair(sp2, tp2, sa, h->tune);
+      if ((rc = run(sp2, buf(TA), sa, buf(MID), sm2, nullptr, true, nullptr, 0, c8b))) return rc;
+      const void* res = cur;
+      if (ds) {
+        if ((rc = run(*ds, cur, cs, buf(DSB), sd, nullptr, false))) return rc;
+        res = buf(DSB);
+      }
+      void* out = buf(outs[li][b]);
+      if ((rc = run(tp2, buf(MID), sm2, out, so, res, true, nullptr, c8b, 0))) return rc;
+      cur = out;
+      cs = so;
+    }
+    taps[li + 1] = cur;
+    taps_shape[li + 1] = cs;
+    // decoder projections at tap resolution (P01 = W0 f0 + W1 f1, P2, P3) on the side stream while
+    // layer4 runs: its convs (600-920 blocks for 30 clips, 1.2-1.8 rounds of the chip's block slots)
+    // leave CUs idle that the projections fill (forked earlier, P01 only shared layer2's full grids:
+    // r03i trace, no gain); P4 after layer4 on s
+    if (li == 2) {
+      if ((rc = run_side(h->proj[0], taps[0], taps_shape[0], buf(P01), sp, taps[1]))) return rc;
+      if ((rc = run_side(h->proj[2], taps[2], taps_shape[2], buf(PP2), sp2, nullptr))) return rc;
+      if ((rc = run_side(h->proj[3], taps[3], taps_shape[3], buf(PP3), sp3, nullptr))) return rc;
+    }
+  }
+  if ((rc = run(h->proj[4], taps[4], taps_shape[4], buf(PP4), sp4, nullptr, false))) return rc;
+  if ((rc = join())) return rc;  // the side stream's projections are complete before the decoder
+
+  const Shape5 tsh[4] = {sp, sp2, sp3, sp4};
+  const int tb[4] = {P01, PP2, PP3, PP4};
+  const float* tp[4];
+  for (int i = 0; i < 4; ++i) tp[i] = reinterpret_cast<const float*>(buf(tb[i]));
+  return decode(tp, tsh, buf(DIDX));
+}
+
+// Whether every launch of a forward over N clips of (T, H, W) is inside its kernel's limits (a CLASFV
+// code; the refusal's reason in clasfv_last_error): the forward's own walk, with nothing launched and
+// no memory behind the addresses (only pointer identity and null-ness are read).
+int forward_fits(const clasfv_engine* h, int N, int T, int H, int W) {
+  if ((int64_t)N * T * H * W >= ((int64_t)1 << 31)) return fail(CLASFV_EBADSHAPE, "the clips have 2^31 voxels or more");
+  Layout L;
+  make_layout(N, T, H, W, L);
+  char* const nowhere = reinterpret_cast<char*>(256);
+  auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
+                 const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
+    const KernelInfo* k = nullptr;
+    return run_conv(c, xin, in, y, out, res, relu, nullptr, nowhere, x2, &k, h->tune, x_c8, y_c8, scratch, scratch_bytes,
+                    true);
+  };
+  auto run_side = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* x2) {
+    return run(c, xin, in, y, out, nullptr, false, x2, 0, 0, nullptr, 0);
+  };
+  auto ok = [](auto...) { return (int)CLASFV_OK; };
+  auto decode = [&](const float* const tp[4], const Shape5 tsh[4], void* idx) {
+    return decoder_addressable(decoder_params(h, tp, tsh, nullptr, nullptr, N, T, H, W, idx))
+               ? (int)CLASFV_OK
+               : fail(CLASFV_EBADSHAPE, "decoder_kernel: a tap has 2^31 floats or more");
+  };
+  return walk_network(h, L, nowhere, N, T, H, W, ok, run, run_side, ok, decode);
+}
+
+// The largest N for which forward_fits (0: not even one clip; the reason stays in clasfv_last_error).
+// Every limit is an upper bound on a size that grows with N, so the fitting N are 1 .. max_clips.
+int max_clips(const clasfv_engine* h, int T, int H, int W) {
+  if (forward_fits(h, 1, T, H, W)) return 0;
+  int64_t lo = 1, hi = ((int64_t)1 << 31) / ((int64_t)T * H * W) + 1;  // fits(lo), !fits(hi)
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) / 2;
+    (forward_fits(h, (int)mid, T, H, W) == CLASFV_OK ? lo : hi) = mid;
+  }
+  return (int)lo;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1116,6 +1327,7 @@ int clasfv_finalize(clasfv_t h) {
     HIP_TRY(hipMemset(h->zero, 0, 256));
   }
   HIP_TRY(hipDeviceSynchronize());
+  h->clip_limit.clear();
   h->ready = true;
   return CLASFV_OK;
 }
@@ -1133,6 +1345,7 @@ int clasfv_set_compute_dtype(clasfv_t h, int dtype) {
   if (dtype != h->dtype) {
     h->dtype = dtype;
     h->ready = false;  // weights must be re-laid-out: call clasfv_finalize again
+    h->clip_limit.clear();
   }
   return CLASFV_OK;
 }
@@ -1144,10 +1357,40 @@ int clasfv_set_kernel_variants(clasfv_t h, int flags) {
   if (flags & ~kVariantMask) return fail(CLASFV_EINVAL, "unknown kernel-variant bit");
   if ((flags ^ h->tune.vflags) & CLASFV_VARIANT_NO_WINOGRAD) h->ready = false;  // weight images change
   h->tune.vflags = flags;
+  h->clip_limit.clear();
   return CLASFV_OK;
 }
 
 int clasfv_get_kernel_variants(clasfv_t h) { return h ? h->tune.vflags : CLASFV_EINVAL; }
+
+// The plan of an engine of this dtype and these variants with every weight image clasfv_finalize would
+// upload marked present: no device is touched, and nothing of it may be launched.
+static int plan_only(clasfv_engine* e, int T, int H, int W, int dtype, int variants) {
+  if (T < 8 || H < 16 || W < 16 || T % 8 || H % 16 || W % 16)
+    return fail(CLASFV_EBADSHAPE, "shape must satisfy T % 8 == 0, H % 16 == 0, W % 16 == 0");
+  if (dtype != CLASFV_DTYPE_FP32 && dtype != CLASFV_DTYPE_BF16) return fail(CLASFV_EINVAL, "unknown dtype");
+  if (variants & ~kVariantMask) return fail(CLASFV_EINVAL, "unknown kernel-variant bit");
+  e->dtype = dtype;
+  e->tune.vflags = variants;
+  build_plan(e);
+  const bool bf16 = dtype == CLASFV_DTYPE_BF16;
+  for (auto& c : e->convs) layout_conv(c, bf16), mark_images(c, bf16, variants);
+  for (auto& c : e->proj) layout_conv(c, bf16), mark_images(c, bf16, variants);
+  return CLASFV_OK;
+}
+
+int clasfv_max_clips(int T, int H, int W, int dtype, int variants) {
+  clasfv_engine e;
+  if (int rc = plan_only(&e, T, H, W, dtype, variants)) return rc;
+  return max_clips(&e, T, H, W);
+}
+
+int clasfv_clips_fit(int N, int T, int H, int W, int dtype, int variants) {
+  if (N < 1) return fail(CLASFV_EINVAL, "N must be >= 1");
+  clasfv_engine e;
+  if (int rc = plan_only(&e, T, H, W, dtype, variants)) return rc;
+  return forward_fits(&e, N, T, H, W);
+}
 
 int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float* seg, float* mot, void* stream) {
   if (!h) return fail(CLASFV_EINVAL, "null handle");
@@ -1157,14 +1400,20 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   if (T < 8 || H < 16 || W < 16 || T % 8 || H % 16 || W % 16)
     return fail(CLASFV_EBADSHAPE, "shape must satisfy T % 8 == 0, H % 16 == 0, W % 16 == 0 (got T=" +
                                       std::to_string(T) + " H=" + std::to_string(H) + " W=" + std::to_string(W) + ")");
+  // The largest batch every kernel of the network can address in one pass (per handle state and clip
+  // shape, kept): a larger N runs as consecutive sub-batches of that many clips. A clip's kernels, and
+  // so its bits, are those of its shape whatever N is.
+  const std::array<int, 3> key{T, H, W};
+  auto hit = h->clip_limit.find(key);
+  if (hit == h->clip_limit.end()) hit = h->clip_limit.emplace(key, max_clips(h, T, H, W)).first;
+  const int nb = std::min(N, hit->second);
+  if (nb < 1) return forward_fits(h, 1, T, H, W);  // one clip of the shape is past a kernel's limit: the reason
   hipStream_t s = (hipStream_t)stream;
   DEVICE_GUARD(h->device);
   Layout L;
-  make_layout(N, T, H, W, L);
+  make_layout(nb, T, H, W, L);
   clasfv_engine::Ctx* cx = nullptr;  // this stream's context
   if (int rc_ = acquire_ctx(h, s, L.total, &cx)) return rc_;
-  char* const arena = cx->arena;
-  auto buf = [&](int b) { return reinterpret_cast<void*>(arena + L.off[b]); };
   int last_ev = h->ktime ? tick(h, s) : -1;
   auto timed = [&](const char* name, double gflop, double xgflop) {
     if (last_ev < 0) return;
@@ -1172,8 +1421,6 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     if (e >= 0) h->recs.push_back({name, gflop, xgflop, last_ev, e});
     last_ev = e;
   };
-  // scratch for a temporal conv reading MID: the rest of MID past its input
-  const size_t mid_bytes = L.off[MID + 1] - L.off[MID];
   if (!cx->side) {
     HIP_TRY(hipStreamCreateWithFlags(&cx->side, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&cx->ev_fork, hipEventDisableTiming));
@@ -1213,95 +1460,48 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     return rc_;
   };
   auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-                 const void* x2 = nullptr, int x_c8 = 0, int y_c8 = 0) {
+                 const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
     const KernelInfo* k = nullptr;
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    if (xin == buf(MID)) {
-      const size_t used = ((size_t)in.n * in.t * in.h * in.w * in.c * sizeof(float) + 255) / 256 * 256;
-      if (used < mid_bytes) {
-        scratch = arena + L.off[MID] + used;
-        scratch_bytes = mid_bytes - used;
-      }
-    }
     log_begin(h);
     int rc_ = run_conv(c, xin, in, y, out, res, relu, s, h->zero, x2, &k, h->tune, x_c8, y_c8, scratch, scratch_bytes);
     log_end(h, conv_index(h, c));
     if (!rc_) timed(k->name, conv_gflop(c, out), k->xgflop(c, out));
     return rc_;
   };
-
-  log_begin(h);
-  HIP_TRY(launch_pack_input(x, reinterpret_cast<float*>(buf(XIN)), N, T, H * W, s));
-  log_end(h, -1);
-  timed("pack_input_kernel", 0.0, 0.0);
-  Shape5 sx{N, T, H, W, 4}, s0, sx0;
-  Shape5 sp, sp2, sp3, sp4;  // decoder tap projections
-  int rc;
-  size_t ci = 0;
-  // Conv2Plus1D mid tensors (and the stem's) are 8-channel-blocked where c8_pair allows
-  const int c8s = c8_pair(h->convs[0], h->convs[1], sx, h->tune);
-  if ((rc = run(h->convs[ci++], buf(XIN), sx, buf(S0), s0, nullptr, true, nullptr, 0, c8s))) return rc;
-  if ((rc = run(h->convs[ci++], buf(S0), s0, buf(X0), sx0, nullptr, true, nullptr, c8s, 0))) return rc;
-  const int outs[4][2] = {{L1A, L1}, {L2A, L2}, {L3A, L3}, {L4A, L4}};
-  void* cur = buf(X0);
-  Shape5 cs = sx0, taps_shape[5];
-  void* taps[5];
-  taps[0] = cur;
-  taps_shape[0] = cs;
-  for (int li = 0; li < 4; ++li) {
-    for (int b = 0; b < 2; ++b) {
-      const Conv& sp1 = h->convs[ci++];
-      const Conv& tp1 = h->convs[ci++];
-      const Conv& sp2 = h->convs[ci++];
-      const Conv& tp2 = h->convs[ci++];
-      const Conv* ds = (ci < h->convs.size() && h->convs[ci].role == DS) ? &h->convs[ci++] : nullptr;
-      Shape5 sm, sa, sm2, so, sd;
-      const int c8a = c8_pair(sp1, tp1, cs, h->tune);
-      if ((rc = run(sp1, cur, cs, buf(MID), sm, nullptr, true, nullptr, 0, c8a))) return rc;
-      if ((rc = run(tp1, buf(MID), sm, buf(TA), sa, nullptr, true, nullptr, c8a, 0))) return rc;
-      const int c8b = c8_pair(sp2, tp2, sa, h->tune);
-      if ((rc = run(sp2, buf(TA), sa, buf(MID), sm2, nullptr, true, nullptr, 0, c8b))) return rc;
-      const void* res = cur;
-      if (ds) {
-        if ((rc = run(*ds, cur, cs, buf(DSB), sd, nullptr, false))) return rc;
-        res = buf(DSB);
-      }
-      void* out = buf(outs[li][b]);
-      if ((rc = run(tp2, buf(MID), sm2, out, so, res, true, nullptr, c8b, 0))) return rc;
-      cur = out;
-      cs = so;
-    }
-    taps[li + 1] = cur;
-    taps_shape[li + 1] = cs;
-    // decoder projections at tap resolution (P01 = W0 f0 + W1 f1, P2, P3) on the side stream while
-    // layer4 runs: its convs (600-920 blocks for 30 clips, 1.2-1.8 rounds of the chip's block slots)
-    // leave CUs idle that the projections fill (forked earlier, P01 only shared layer2's full grids:
-    // r03i trace, no gain); P4 after layer4 on s
-    if (li == 2) {
-      if ((rc = run_side(h->proj[0], taps[0], taps_shape[0], buf(P01), sp, taps[1]))) return rc;
-      if ((rc = run_side(h->proj[2], taps[2], taps_shape[2], buf(PP2), sp2, nullptr))) return rc;
-      if ((rc = run_side(h->proj[3], taps[3], taps_shape[3], buf(PP3), sp3, nullptr))) return rc;
-    }
+  auto join = [&]() {
+    HIP_TRY(side_join.join());
+    return (int)CLASFV_OK;
+  };
+  for (int n0 = 0; n0 < N; n0 += nb) {
+    const int n = std::min(nb, N - n0);
+    // the last, shorter sub-batch runs in the layout of a forward of its own size (it fits the arena)
+    if (n != nb) make_layout(n, T, H, W, L);
+    const size_t clip = (size_t)T * H * W;
+    const float* xs = x + (size_t)n0 * 3 * clip;
+    float *segs = seg + (size_t)n0 * 2 * clip, *mots = mot + (size_t)n0 * 4 * clip;
+    auto pack = [&](void* xin) {
+      log_begin(h);
+      HIP_TRY(launch_pack_input(xs, reinterpret_cast<float*>(xin), n, T, H * W, s));
+      log_end(h, -1);
+      timed("pack_input_kernel", 0.0, 0.0);
+      return (int)CLASFV_OK;
+    };
+    auto decode = [&](const float* const tp[4], const Shape5 tsh[4], void* idx) {
+      const DecParams d = decoder_params(h, tp, tsh, segs, mots, n, T, H, W, idx);
+      log_begin(h);
+      HIP_TRY(launch_decoder(d, s));
+      log_end(h, -1);
+      // comb_2 (64x64) and the heads (6 useful of the 16 rows of their MFMA tile) per output voxel, in the
+      // products of the pipe they run on: fp32 engines six split-bf16 products each (bf16 pipe), bf16
+      // engines three for comb_2 and six for the heads (bf16 pipe), the no_decoder_x3 variant one f32
+      // product each (f32 pipe)
+      const double dec_px = d.x3 ? 6.0 * (64 * 64 + 64 * 16) : d.bf16 ? 3.0 * 64 * 64 + 6.0 * 64 * 16 : 64 * 64 + 64 * 16;
+      timed(d.x3 || d.bf16 ? "decoder_kernel" : "decoder_kernel_f32", 2.0 * n * (double)T * H * W * (64 * 64 + 64 * 6) * 1e-9,
+            2.0 * n * (double)T * H * W * dec_px * 1e-9);
+      return (int)CLASFV_OK;
+    };
+    if (int rc = walk_network(h, L, cx->arena, n, T, H, W, pack, run, run_side, join, decode)) return rc;
   }
-  if ((rc = run(h->proj[4], taps[4], taps_shape[4], buf(PP4), sp4, nullptr, false))) return rc;
-  HIP_TRY(side_join.join());  // the side stream's projections are complete before the decoder
-
-  const Shape5 tsh[4] = {sp, sp2, sp3, sp4};
-  const int tb[4] = {P01, PP2, PP3, PP4};
-  const float* tp[4];
-  for (int i = 0; i < 4; ++i) tp[i] = reinterpret_cast<const float*>(buf(tb[i]));
-  const DecParams d = decoder_params(h, tp, tsh, seg, mot, N, T, H, W, buf(DIDX));
-  log_begin(h);
-  HIP_TRY(launch_decoder(d, s));
-  log_end(h, -1);
-  // comb_2 (64x64) and the heads (6 useful of the 16 rows of their MFMA tile) per output voxel, in the
-  // products of the pipe they run on: fp32 engines six split-bf16 products each (bf16 pipe), bf16
-  // engines three for comb_2 and six for the heads (bf16 pipe), the no_decoder_x3 variant one f32
-  // product each (f32 pipe)
-  const double dec_px = d.x3 ? 6.0 * (64 * 64 + 64 * 16) : d.bf16 ? 3.0 * 64 * 64 + 6.0 * 64 * 16 : 64 * 64 + 64 * 16;
-  timed(d.x3 || d.bf16 ? "decoder_kernel" : "decoder_kernel_f32", 2.0 * N * (double)T * H * W * (64 * 64 + 64 * 6) * 1e-9,
-        2.0 * N * (double)T * H * W * dec_px * 1e-9);
   return CLASFV_OK;
 }
 
@@ -1433,13 +1633,6 @@ int clasfv_run_decoder(clasfv_t h, const float* p01, const float* p2, const floa
   if (N < 1 || T < 1 || H < 2 || W < 2) return fail(CLASFV_EINVAL, "bad shape");
   if (H % 8 || W % 16) return fail(CLASFV_EBADSHAPE, "decoder tiles: H % 8 == 0 and W % 16 == 0");
   hipStream_t s = (hipStream_t)stream;
-  DEVICE_GUARD(h->device);
-  // the index table lives where the forward keeps it: in this stream's arena, sized and laid out for a
-  // whole forward of this shape (a later clasfv_forward of the shape reuses the arena as it stands)
-  Layout L;
-  make_layout(N, T, H, W, L);
-  clasfv_engine::Ctx* cx = nullptr;
-  if (int rc = acquire_ctx(h, s, L.total, &cx)) return rc;
   // tap resolutions as the backbone produces them: the stem halves H and W, layer2..4 halve T, H, W
   // (3-wide kernels, stride 2, padding 1: d -> (d - 1) / 2 + 1)
   auto half = [](int d) { return (d - 1) / 2 + 1; };
@@ -1450,6 +1643,16 @@ int clasfv_run_decoder(clasfv_t h, const float* p01, const float* p2, const floa
     if (k) t = half(t), hh = half(hh), ww = half(ww);
     tsh[k] = Shape5{N, t, hh, ww, 64};
   }
+  if (!decoder_addressable(decoder_params(h, taps, tsh, seg, mot, N, T, H, W, nullptr)))
+    return fail(CLASFV_EBADSHAPE, "decoder_kernel: every tap must have fewer than 2^31 floats, and the grid fewer than "
+                                  "2^31 blocks");
+  DEVICE_GUARD(h->device);
+  // the index table lives where the forward keeps it: in this stream's arena, sized and laid out for a
+  // whole forward of this shape (a later clasfv_forward of the shape reuses the arena as it stands)
+  Layout L;
+  make_layout(N, T, H, W, L);
+  clasfv_engine::Ctx* cx = nullptr;
+  if (int rc = acquire_ctx(h, s, L.total, &cx)) return rc;
   log_begin(h);
   HIP_TRY(launch_decoder(decoder_params(h, taps, tsh, seg, mot, N, T, H, W, cx->arena + L.off[DIDX]), s));
   log_end(h, -1);

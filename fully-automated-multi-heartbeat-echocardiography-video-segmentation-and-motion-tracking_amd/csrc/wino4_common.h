@@ -54,6 +54,13 @@ static_assert(W4_ZBYTES <= W4Ring<4>::LDS && W4Ring<4>::LDS <= 80 * 1024 && W4Ri
                   W4Ring<6>::LDS <= 80 * 1024,
               "two blocks per CU");
 
+// The raw-patch DMAs read the input through one buffer resource in 32-bit byte offsets, and byte offset
+// 2^31 is their "read zeros" slot (padding pixels, dead slots): the whole input ends below it, so that
+// the offset is out of the resource's range (the stores are 64-bit and carry no such limit).
+inline bool wino4_input_fits(const ConvParams& p) {
+  return (size_t)p.N * p.Ti * p.Hi * p.Wi * p.Cin * sizeof(float) < ((size_t)1 << 31);
+}
+
 __device__ inline int xcd_swizzle4(int b, int nb) {
   const int q = nb >> 3, r = nb & 7, x = b & 7, i = b >> 3;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;

@@ -408,7 +408,7 @@ bool wino4_supported(const ConvParams& p) {
   return !p.in_bf16 && !p.out_bf16 && !p.stem && !p.x2 && !p.res && p.KT == 1 && p.KH == 3 && p.KW == 3 &&
          p.sh == 1 && p.sw == 1 && p.st == 1 && p.ph == 1 && p.pw == 1 && p.pt == 0 && p.Ho == p.Hi &&
          p.Wo == p.Wi && p.To == p.Ti && (size_t)p.N * p.To * p.Ho * p.Wo * (p.Cin > p.Cout ? p.Cin : p.Cout) <
-         ((size_t)1 << 31) && wino4_geometry(p, &g, &nb, 48, W4_FILL);
+         ((size_t)1 << 31) && wino4_input_fits(p) && wino4_geometry(p, &g, &nb, 48, W4_FILL);
 }
 
 // p.w: wino4_transform_weights' layout. (The launch templates are called from this non-template

@@ -911,7 +911,7 @@ bool wino4w_supported(const ConvParams& p) {
          p.sh == 1 && p.sw == 1 && p.st == 1 && p.ph == 1 && p.pw == 1 && p.pt == 0 && p.Ho == p.Hi &&
          p.Wo == p.Wi && p.To == p.Ti &&
          (size_t)p.N * p.To * p.Ho * p.Wo * (p.Cin > p.Cout ? p.Cin : p.Cout) < ((size_t)1 << 31) &&
-         wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL);
+         wino4_input_fits(p) && wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL);
 }
 
 // p.w: wino4w_transform_weights' layout for this Cout's NTN.
@@ -994,7 +994,7 @@ bool wino4r_supported(const ConvParams& p) {
          p.sh == 1 && p.sw == 1 && p.st == 1 && p.ph == 1 && p.pw == 1 && p.pt == 0 && p.Ho == p.Hi &&
          p.Wo == p.Wi && p.To == p.Ti &&
          (size_t)p.N * p.To * p.Ho * p.Wo * (p.Cin > p.Cout ? p.Cin : p.Cout) < ((size_t)1 << 31) &&
-         wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL) && g.LNI <= W4R_MAX_LNI;  // (every group of <= 16 tiles: <= 74)
+         wino4_input_fits(p) && wino4_geometry(p, &g, &nb, 16 * ntn, W4W_FILL) && g.LNI <= W4R_MAX_LNI;  // (every group of <= 16 tiles: <= 74)
 }
 
 // Start stagger of a launch: on grids of >= 16 blocks per CU (layer1 at >= 11 clips of 32 x 112 x 112) the

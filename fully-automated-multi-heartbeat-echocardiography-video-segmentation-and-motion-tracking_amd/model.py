@@ -160,6 +160,14 @@ class Engine:
         return {names[i].decode(): {"launches": int(launches[i]), "ms": float(ms[i]), "gflop": float(gf[i]),
                                     "xgflop": float(xg[i])} for i in range(n)}
 
+    def max_clips(self, t, h, w):
+        """The largest batch of (t, h, w) clips one pass of the network takes with this engine's dtype and
+        variants (clasfv_max_clips); forward() runs a larger one as sub-batches of that many clips."""
+        n = self.lib.clasfv_max_clips(t, h, w, _lib.DTYPES[self.dtype], self.lib.clasfv_get_kernel_variants(self.h))
+        if n < 0:
+            _lib.check(n, "clasfv_max_clips")
+        return n
+
     def workspace_bytes(self):
         return int(self.lib.clasfv_workspace_bytes(self.h))
 

@@ -34,7 +34,8 @@ extern "C" {
 enum {
   CLASFV_OK = 0,
   CLASFV_EINVAL = -1,     /* bad argument / unknown parameter name */
-  CLASFV_EBADSHAPE = -2,  /* shape not supported: T % 8, H % 16, W % 16 must be 0 (forward); frame too large (SIMPLE) */
+  CLASFV_EBADSHAPE = -2,  /* shape not supported: T % 8, H % 16, W % 16 must be 0 (forward); frame too large (SIMPLE);
+                             a tensor past what the kernel addresses (see "Size limits" below) */
   CLASFV_ENOTREADY = -3,  /* forward before clasfv_finalize / missing parameters */
   CLASFV_EHIP = -4,       /* HIP runtime error (message in clasfv_last_error) */
   CLASFV_ENOMEM = -5
@@ -112,12 +113,28 @@ int clasfv_finalize(clasfv_t h);
    Stream-ordered on `stream` (a hipStream_t; NULL = the default stream), no host synchronisation.
    The handle keeps one workspace per launch stream (up to 4; a fifth stream takes over the least
    recently used one after a device synchronisation), so forwards issued on different streams may run
-   concurrently; calls on one handle must come from one host thread at a time. */
+   concurrently; calls on one handle must come from one host thread at a time.
+   Size limits: every kernel addresses its tensors in 32 bits somewhere ("Size limits"), and
+   nothing is launched outside those limits. N is not limited by them: a batch of more clips than
+   clasfv_max_clips reports for the shape runs as consecutive sub-batches of that many clips (the
+   workspace is sized for one sub-batch), and a clip's outputs are bit-identical whatever N is.
+   CLASFV_EBADSHAPE, before the first launch, when a single clip of the shape is past a limit
+   (clasfv_max_clips == 0: for instance T * H * W >= 2^31). */
 int clasfv_forward(clasfv_t h, const float* x_dev, int N, int T, int H, int W, float* seg_dev,
                    float* motion_dev, void* stream);
 /* Bytes of library workspace currently held (the per-stream activation arenas; each grows to the
    largest N*T*H*W seen on its stream). */
 int64_t clasfv_workspace_bytes(clasfv_t h);
+/* The largest number of (T, H, W) clips one pass of the network takes, for an engine of compute dtype
+ * `dtype` (CLASFV_DTYPE_*) and kernel variants `variants` (CLASFV_VARIANT_* bits): the largest N for which
+ * every launch of clasfv_forward stays inside its kernel's addressing limits on the kernel a single clip
+ * of the shape runs on. 0 when one clip is already past a limit; CLASFV_EBADSHAPE / CLASFV_EINVAL for
+ * a shape clasfv_forward does not take / an unknown dtype or variant bit. Host arithmetic only: needs
+ * neither a handle nor a device. New export only: the ABI revision is unchanged. */
+int clasfv_max_clips(int T, int H, int W, int dtype, int variants);
+/* The test clasfv_max_clips searches with: CLASFV_OK when every launch of one pass over N clips is inside
+ * its kernel's limits, CLASFV_EBADSHAPE (the first launch that is not, in clasfv_last_error) otherwise. */
+int clasfv_clips_fit(int N, int T, int H, int W, int dtype, int variants);
 /* Compute dtype of the encoder: CLASFV_DTYPE_FP32 (default; exact-fp32 MFMA, the reference's
  * precision) or CLASFV_DTYPE_BF16 (bf16 activations/weights, fp32 accumulation; BASELINE config[4],
  * Dice tolerance 1e-2). The decoder head runs in fp32 either way. A change takes effect at the next
@@ -185,13 +202,19 @@ int clasfv_conv_info(clasfv_t h, int i, const char** prefix, const char** bn_pre
  * alias y) the same over the conv's output voxels and cout_p; x2 the second input of P01 (NULL
  * otherwise); dtypes as clasfv_conv_info reports. scratch: split-K partial sums (4 * M * cout_p
  * floats enable it; NULL / 0: never split). *kernel_name: the kernel that ran (static string).
- * CLASFV_EINVAL for a layout the chosen kernel does not take. */
+ * CLASFV_EINVAL for a layout the chosen kernel does not take. The kernel is the one a single clip of
+ * (T, H, W) runs on; CLASFV_EBADSHAPE, with nothing launched and *kernel_name set to that kernel, when
+ * the N clips are past what it addresses (2^31 input bytes for the F(4x4) kernels, 2^31 elements for
+ * conv_wino_q / conv_wino / conv_winot / conv_twalk_bf16, 2^30 voxels for the bf16 patch kernels, 2^32
+ * input elements for conv_dma / conv_dma_x3) or when the input or the output has 2^31 voxels or more. */
 int clasfv_run_conv(clasfv_t h, int i, const void* x_dev, int N, int T, int H, int W, const void* x2_dev,
                     const void* res_dev, int relu, int x_c8, int y_c8, void* y_dev, void* scratch_dev,
                     int64_t scratch_bytes, const char** kernel_name, void* stream);
 /* Run the decoder alone over caller-supplied 64-channel projected taps (channels-last fp32) with the
  * handle's head weights: p01 at (T, H', W'), H' = (H - 1) / 2 + 1, and p2, p3, p4 each halving T, H'
- * and W' again the same way (d -> (d - 1) / 2 + 1). H % 8 == 0 and W % 16 == 0 (CLASFV_EBADSHAPE). */
+ * and W' again the same way (d -> (d - 1) / 2 + 1). H % 8 == 0 and W % 16 == 0, every tap below 2^31
+ * floats and the grid N * T * (H / 8) * (W / 16) below 2^31 blocks (CLASFV_EBADSHAPE, before any launch or
+ * allocation). */
 int clasfv_run_decoder(clasfv_t h, const float* p01_dev, const float* p2_dev, const float* p3_dev,
                        const float* p4_dev, int N, int T, int H, int W, float* seg_dev, float* motion_dev,
                        void* stream);

@@ -120,3 +120,62 @@ def test_fill_workspace_rejects_a_null_handle():
     assert lib.clasfv_fill_workspace(None, 0xFF, None) == -1
     assert b"null handle" in lib.clasfv_last_error()
     assert lib.clasfv_workspace_bytes(None) == 0
+
+
+# ---- size limits: max_clips and the gates behind it (host arithmetic, no device) ---------------------------
+LIM31 = 1 << 31
+
+
+def _closed_form(dtype, t, h, w):
+    """The limit that binds at the network's shapes, by DESIGN.md's "Size limits" table. fp32: the 64-channel
+    fp32 input of layer1's F(4x4,3x3) convs, (t, h/2, w/2), ends below byte 2^31 (the kernels' "read zeros"
+    slot). bf16: the decoder's P01 tap, 64 fp32 channels at (t, h/2, w/2), has fewer than 2^31 floats."""
+    vox = t * (h // 2) * (w // 2)
+    return (LIM31 - 1) // (vox * 64 * 4) if dtype == 0 else (LIM31 - 1) // (vox * 64)
+
+
+def test_max_clips_at_the_product_shapes_and_which_limit_binds():
+    from clasfv_amd import _lib
+    lib = _lib.load()
+    want = {(0, 64, 224, 224): 10, (0, 32, 112, 112): 83, (1, 64, 224, 224): 41, (1, 32, 112, 112): 334}
+    for (dtype, t, h, w), n in want.items():
+        assert _closed_form(dtype, t, h, w) == n
+        assert lib.clasfv_max_clips(t, h, w, dtype, 0) == n
+        assert lib.clasfv_clips_fit(n, t, h, w, dtype, 0) == 0
+        assert lib.clasfv_clips_fit(n + 1, t, h, w, dtype, 0) == -2
+        msg = lib.clasfv_last_error()
+        assert (b"conv_wino4r" if dtype == 0 else b"decoder_kernel") in msg, msg
+    # other clips whose layer1 maps F(4x4,3x3) serves: the same closed forms
+    for t, h, w in ((8, 32, 48), (16, 80, 112), (24, 64, 64)):
+        for dtype in (0, 1):
+            assert lib.clasfv_max_clips(t, h, w, dtype, 0) == _closed_form(dtype, t, h, w), (dtype, t, h, w)
+    # 8 x 8 maps in layer1 (<= 64 pixels) run the split-bf16 direct GEMM instead: the temporal Winograd's 2^31
+    # elements of the 144-channel mid tensor bind
+    assert lib.clasfv_max_clips(8, 16, 16, 0, 0) == (LIM31 - 1) // (8 * 8 * 8 * 144) == 29127
+
+
+def test_clips_fit_is_monotone_in_the_batch():
+    """Every limit bounds a size that grows with N: N fits exactly when N <= max_clips, whatever the variants
+    (each moves the binding limit to another kernel)."""
+    from clasfv_amd import _lib
+    lib = _lib.load()
+    V = _lib.VARIANTS
+    for dtype, variants in ((0, 0), (1, 0), (0, V["no_wino4"]), (0, V["no_winograd"]), (0, V["no_dma_x3"] | V["no_wino4r"]),
+                            (1, V["no_patch_bf16"]), (1, V["no_twalk"] | V["no_dma_w"])):
+        t, h, w = 32, 112, 112
+        mc = lib.clasfv_max_clips(t, h, w, dtype, variants)
+        assert 1 <= mc <= _closed_form(1, t, h, w)  # the decoder's tap bounds every configuration
+        fits = [lib.clasfv_clips_fit(n, t, h, w, dtype, variants) == 0
+                for n in (1, 2, mc // 2, mc - 1, mc, mc + 1, mc + 2, 2 * mc, 10 * mc, LIM31 // (t * h * w) + 5)]
+        assert fits == [True] * 5 + [False] * 5, (dtype, variants, mc, fits)
+
+
+def test_max_clips_arguments_and_a_clip_no_pass_serves():
+    from clasfv_amd import _lib
+    lib = _lib.load()
+    assert lib.clasfv_max_clips(8, 16384, 16384, 0, 0) == 0  # one clip of 2^31 voxels: M is an int
+    assert lib.clasfv_max_clips(8, 16384, 16384, 1, 0) == 0
+    assert lib.clasfv_max_clips(8, 8192, 16384, 0, 0) == 0   # 2^30 voxels: the stem's 48-channel tensor alone passes 2^31 elements
+    assert lib.clasfv_max_clips(12, 32, 32, 0, 0) == -2 and lib.clasfv_max_clips(8, 32, 40, 0, 0) == -2
+    assert lib.clasfv_max_clips(8, 32, 32, 2, 0) == -1 and lib.clasfv_max_clips(8, 32, 32, 0, 1 << 17) == -1
+    assert lib.clasfv_clips_fit(0, 8, 32, 32, 0, 0) == -1
