@@ -10,6 +10,32 @@ from .build import LIB_PATH
 c_int, c_int64, c_void_p, c_char_p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p
 _P = c_void_p
 
+PLAN_MAX_RANGES = 8  # CLASFV_PLAN_MAX_RANGES
+# CLASFV_PLAN_* kinds, range roles and the caller's tensors' buffer ids (include/clasfv.h)
+PLAN_KINDS = ("pack", "conv", "split_sum", "dec_index", "decoder", "fork", "join")
+PLAN_ROLES = ("x", "x2", "res", "y", "part", "idx", "tap")
+PLAN_EXTERNAL = {-1: "clip", -2: "seg", -3: "motion"}
+
+
+class PlanRange(ctypes.Structure):  # clasfv_plan_range_t
+    _fields_ = [("buffer", ctypes.c_int32), ("role", ctypes.c_int32), ("write", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("offset", c_int64), ("bytes", c_int64)]
+
+
+class PlanLaunch(ctypes.Structure):  # clasfv_plan_launch_t
+    _fields_ = [("sub_batch", ctypes.c_int32), ("stream", ctypes.c_int32), ("kind", ctypes.c_int32),
+                ("conv", ctypes.c_int32), ("kernel", c_char_p), ("split_asked", ctypes.c_int32),
+                ("split_granted", ctypes.c_int32), ("x_c8", ctypes.c_int32), ("y_c8", ctypes.c_int32),
+                ("relu", ctypes.c_int32), ("has_res", ctypes.c_int32), ("x_elem", ctypes.c_int32),
+                ("y_elem", ctypes.c_int32), ("n_ranges", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("range", PlanRange * PLAN_MAX_RANGES)]
+
+
+class PlanBuffer(ctypes.Structure):  # clasfv_plan_buffer_t
+    _fields_ = [("sub_batch", ctypes.c_int32), ("clips", ctypes.c_int32), ("id", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("name", c_char_p), ("offset", c_int64), ("bytes", c_int64), ("total", c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/clasfv.h
 SIGNATURES = {
     "clasfv_last_error": (c_char_p, []),
@@ -37,6 +63,11 @@ SIGNATURES = {
     "clasfv_launch_log": (c_int, [_P, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int64), ctypes.POINTER(c_int),
                                   ctypes.POINTER(c_int)]),
     "clasfv_fill_workspace": (c_int, [_P, c_int, _P]),
+    "clasfv_workspace_view": (c_int, [_P, _P, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64)]),
+    "clasfv_forward_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(PlanLaunch),
+                                    ctypes.POINTER(c_int), c_int, ctypes.POINTER(PlanBuffer), ctypes.POINTER(c_int)]),
+    "clasfv_plan_conv_info": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                      ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "clasfv_conv_count": (c_int, [_P]),
     "clasfv_conv_info": (c_int, [_P, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_char_p), ctypes.POINTER(c_int),
                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),

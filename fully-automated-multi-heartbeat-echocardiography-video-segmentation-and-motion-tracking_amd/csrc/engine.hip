@@ -145,6 +145,9 @@ void mark_images(Conv& c, bool bf16, int vflags) {
   const Images m = images_of(c, bf16, vflags);
   void* const some = &c;
   c.dw = some;
+  // the folded-BN bias of a backbone conv (the projections have none): stem_bf16_supported asks for it, and
+  // without it the device-less plan put the bf16 engines' stem on conv_stem_f32
+  c.db = c.role != PROJ ? reinterpret_cast<float*>(some) : nullptr;
   c.dx3 = m.x3 ? some : nullptr;
   c.dwino = m.wino ? some : nullptr;
   c.dwino4 = m.wino4 ? some : nullptr;
@@ -781,10 +784,14 @@ Kernel pick_kernel(const Conv& c, ConvParams p) {
 // Whether the mid tensor between producer `a` (input shape `in`) and consumer `b` goes through HBM
 // in the 8-channel-blocked layout: `a` runs on a kernel that writes it and `b` on one that reads it
 // (conv_winot where launch_winot takes conv_winot5; CLASFV_VARIANT_NO_C8: always channels-last).
-// The choice depends on shapes and flags only: no *_supported test reads ConvParams::w.
-bool c8_pair(const Conv& a, const Conv& b, const Shape5& in, const Tuning& tu) {
+// The choice depends on flags and on the shape of one clip only, never on the batch (no *_supported test
+// reads ConvParams::w): a batch whose blocked mid tensor conv_winot5 cannot address is refused by
+// run_conv, like a batch past any other limit of a clip's kernel, so max_clips stops below it and a
+// clip's launches, layouts included, are those of its shape whatever N is.
+bool c8_pair(const Conv& a, const Conv& b, const Shape5& in_batch, const Tuning& tu) {
   if (tu.vflags & CLASFV_VARIANT_NO_C8) return false;
-  Shape5 mid, out;
+  Shape5 in = in_batch, mid, out;
+  in.n = 1;
   ConvParams pa = conv_params(a, in, mid);
   ConvParams pb = conv_params(b, mid, out);
   pa.vflags = pb.vflags = tu.vflags;
@@ -808,9 +815,11 @@ void split_k(ConvParams& p, int S, void* scratch, size_t scratch_bytes) {
 //  * The kernel is the one a single clip of the shape runs on. The size clauses of the gates would
 //    otherwise hand a large batch to the next kernel of pick_kernel's list, often one of another rounding
 //    family (F(4x4) -> F(2x2) -> conv_dma_x3), and a clip's bits would depend on its batch.
-//    (launch_winot's conv_winot5 -> conv_winot, the buffer -> pointer forms of conv_dma / conv_dma_x3 and
-//    conv_dma_w -> conv_dma, whose buffer DMAs end at 2^31 bytes, are switches between bit-identical
-//    forms of one kernel, and stay: k is the batch's kernel then.)
+//    conv_dma_w -> conv_dma, at the 2^31 bytes where conv_dma_w's buffer DMAs end, is refused like the rest
+//    although the two are bit-identical: the launch plan promises one kernel name per conv whatever N is.
+//    (launch_winot's conv_winot5 -> conv_winot over a channels-last input and the buffer -> pointer forms
+//    of conv_dma / conv_dma_x3 are switches between bit-identical forms of one kernel, made inside its
+//    launcher, and stay.)
 //  * gemm_size_error, once split-K is decided -- the implicit GEMMs (the list's last resort, so nothing
 //    catches what they cannot address): their pointer forms offset x and x2 by 32-bit element counts,
 //    and their grid is an int.
@@ -818,7 +827,7 @@ const char* conv_size_error(Kernel k, Kernel kn, const Shape5& in, const Shape5&
   constexpr int64_t k31 = (int64_t)1 << 31;
   if (out.voxels() >= k31) return "the output has 2^31 voxels or more";
   if (in.voxels() >= k31) return "the input has 2^31 voxels or more";
-  if (kn != k && !(k == K_DMA_W && kn == K_DMA))
+  if (kn != k)
     return "the batch is past the size limit of the kernel one clip of this shape runs on";
   return nullptr;
 }
@@ -834,11 +843,20 @@ const char* gemm_size_error(const KernelInfo& k, const ConvParams& p, const Shap
   return nullptr;
 }
 
+// What run_conv decided, for a caller that records it (clasfv_forward_plan): the parameters the launcher
+// takes and the split-K factor the per-clip rule asked for (p.n_split is the one granted).
+struct ConvBuilt {
+  ConvParams p;
+  int split_asked;
+};
+
 // Runs c on the kernel pick_kernel chooses; *kernel is its kKernels row once chosen. A shape that kernel
 // cannot address is refused (CLASFV_EBADSHAPE) before anything is launched; dry: stop after that check.
+// *built, when given, is what the launcher is (or, dry, would be) called with.
 int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
              hipStream_t s, const void* zero_block, const void* x2, const KernelInfo** kernel, const Tuning& tu,
-             int x_c8 = 0, int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0, bool dry = false) {
+             int x_c8 = 0, int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0, bool dry = false,
+             ConvBuilt* built = nullptr) {
   if (in.c != c.cin_p) return fail(CLASFV_EINVAL, "internal: channel mismatch");
   ConvParams p = conv_params(c, in, out);
   p.vflags = tu.vflags;
@@ -862,8 +880,7 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
     return fail(CLASFV_EBADSHAPE, std::string(k1.name) + ": " + why + " (N=" + std::to_string(in.n) + " T=" +
                                       std::to_string(in.t) + " H=" + std::to_string(in.h) + " W=" + std::to_string(in.w) +
                                       " C=" + std::to_string(in.c) + ")");
-  const KernelInfo& k = kKernels[kn];  // k1, or conv_dma for conv_dma_w
-  *kernel = &k;
+  const KernelInfo& k = k1;
   if ((y_c8 && !k.writes_c8) || (x_c8 && !k.reads_c8))
     return fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
   if (x_c8 && k.id == K_WINOT && !winot_c8_ok(p))  // only launch_winot's conv_winot5 form reads the layout
@@ -871,16 +888,22 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
                            : fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
   p.w = c.*k.image;
   int mt = 2, bn = 0;  // the implicit GEMMs' tile
+  int asked = 1;       // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
   if (k.id == K_WINOT) {
-    // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
-    split_k(p, winot_split_for(p), scratch, scratch_bytes);
+    asked = winot_split_for(p);
   } else if (k.id == K_DMA_X3) {
-    split_k(p, dma_split_for(p, 2), scratch, scratch_bytes);
+    asked = dma_split_for(p, 2);
   } else if (k.id == K_DMA_W || k.id == K_DMA) {
     conv_pick_tile(p.M, c.cout_p, tu.conv_nt, &mt, &bn);
-    split_k(p, dma_split_for(p, mt), scratch, scratch_bytes);
+    asked = dma_split_for(p, mt);
   }
+  // A caller that offers no scratch asks for no split (clasfv_run_conv's contract, and the walk's for every
+  // conv that does not read MID); one that offers it is owed the rule's factor, and a scratch too small
+  // for the sums shows as split_asked > n_split in the plan (tests/plan_audit.py, check E).
+  if (!scratch) asked = 1;
+  split_k(p, asked, scratch, scratch_bytes);
   if (const char* why = gemm_size_error(k, p, in, out)) return fail(CLASFV_EBADSHAPE, std::string(k.name) + ": " + why);
+  if (built) *built = ConvBuilt{p, asked > 1 ? asked : 1};
   if (dry) return CLASFV_OK;
   switch (k.id) {  // no default: a Kernel without a launch is a compiler warning
     case K_WINO4R: HIP_TRY(launch_wino4r(p, s)); break;
@@ -908,9 +931,12 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
 // Workspace layout for one (N,T,H,W).
 struct Layout {
   size_t off[32];
+  size_t bytes[32];  // of each buffer, without the slack up to the next one
   size_t total;
 };
 enum Buf { XIN, S0, X0, MID, TA, DSB, L1A, L1, L2A, L2, L3A, L3, L4A, L4, P01, PP2, PP3, PP4, DIDX, NBUF };
+constexpr const char* kBufNames[NBUF] = {"XIN", "S0",  "X0", "MID", "TA",  "DSB", "L1A", "L1",  "L2A", "L2",
+                                         "L3A", "L3",  "L4A", "L4", "P01", "PP2", "PP3", "PP4", "DIDX"};
 
 void make_layout(int N, int T, int H, int W, Layout& L) {
   const size_t T1 = T, H2 = H / 2, W2 = W / 2;
@@ -941,7 +967,8 @@ void make_layout(int N, int T, int H, int W, Layout& L) {
   size_t o = 0;
   for (int i = 0; i < NBUF; ++i) {
     L.off[i] = o;
-    o += (sz[i] * sizeof(float) + 255) / 256 * 256;
+    L.bytes[i] = sz[i] * sizeof(float);
+    o += (L.bytes[i] + 255) / 256 * 256;
   }
   L.total = o;
 }
@@ -1119,12 +1146,13 @@ int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, in
                  const void* x2 = nullptr, int x_c8 = 0, int y_c8 = 0) {
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
+    // Which convs may split is a property of the walk, not of sizes: those that read MID (the temporal
+    // convs) are offered what is left of it, even when that is nothing, and no other conv is offered any.
     if (xin == buf(MID)) {
-      const size_t used = ((size_t)in.n * in.t * in.h * in.w * in.c * sizeof(float) + 255) / 256 * 256;
-      if (used < mid_bytes) {
-        scratch = arena + L.off[MID] + used;
-        scratch_bytes = mid_bytes - used;
-      }
+      const size_t used =
+          std::min(mid_bytes, ((size_t)in.n * in.t * in.h * in.w * in.c * sizeof(float) + 255) / 256 * 256);
+      scratch = arena + L.off[MID] + used;
+      scratch_bytes = mid_bytes - used;
     }
     return run_(c, xin, in, y, out, res, relu, x2, x_c8, y_c8, scratch, scratch_bytes);
   };
@@ -1188,6 +1216,32 @@ int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, in
   return decode(tp, tsh, buf(DIDX));
 }
 
+// The sub-batches of an N-clip call whose passes take nb clips each: body(sub, n0, n, L) for clips
+// [n0, n0 + n) on the layout L of a forward of n clips. The last, shorter sub-batch runs in the layout
+// of a forward of its own size (it fits the arena, which is sized for nb). The first failure ends the
+// loop. clasfv_forward launches through it and clasfv_forward_plan records through it.
+template <class Body>
+int for_sub_batches(int N, int nb, int T, int H, int W, Body body) {
+  Layout L;
+  make_layout(nb, T, H, W, L);
+  int sub = 0;
+  for (int n0 = 0; n0 < N; n0 += nb, ++sub) {
+    const int n = std::min(nb, N - n0);
+    if (n != nb) make_layout(n, T, H, W, L);
+    if (int rc = body(sub, n0, n, L)) return rc;
+  }
+  return CLASFV_OK;
+}
+
+// Where the clips of a sub-batch that starts at clip n0 begin in the caller's tensors, in elements.
+struct CallerOffsets {
+  size_t x, seg, mot;
+};
+CallerOffsets caller_offsets(int n0, int T, int H, int W) {
+  const size_t clip = (size_t)T * H * W;
+  return {(size_t)n0 * 3 * clip, (size_t)n0 * 2 * clip, (size_t)n0 * 4 * clip};
+}
+
 // Whether every launch of a forward over N clips of (T, H, W) is inside its kernel's limits (a CLASFV
 // code; the refusal's reason in clasfv_last_error): the forward's own walk, with nothing launched and
 // no memory behind the addresses (only pointer identity and null-ness are read).
@@ -1224,6 +1278,117 @@ int max_clips(const clasfv_engine* h, int T, int H, int W) {
     (forward_fits(h, (int)mid, T, H, W) == CLASFV_OK ? lo : hi) = mid;
   }
   return (int)lo;
+}
+
+// ---- the launch plan (clasfv_forward_plan) ------------------------------------------------------------
+// clasfv_forward's sub-batch loop and walk with runners that record instead of launching: run_conv in
+// its dry mode hands back the ConvParams its launcher would take, and every range below is what those
+// parameters (or the decoder's) make the kernel address. No memory is behind the addresses.
+struct PlanRecorder {
+  std::vector<clasfv_plan_launch_t> launches;
+  std::vector<clasfv_plan_buffer_t> buffers;
+};
+
+int forward_plan(const clasfv_engine* h, int N, int T, int H, int W, PlanRecorder& rec) {
+  const int nb = std::min(N, max_clips(h, T, H, W));
+  if (nb < 1) return forward_fits(h, 1, T, H, W);
+  char* const arena = reinterpret_cast<char*>(256);
+  bool side_pending = false;  // SideJoin::pending of clasfv_forward
+  return for_sub_batches(N, nb, T, H, W, [&](int sub, int n0, int n, const Layout& L) {
+    for (int b = 0; b < NBUF; ++b)
+      rec.buffers.push_back({sub, n, b, 0, kBufNames[b], (int64_t)L.off[b], (int64_t)L.bytes[b], (int64_t)L.total});
+    auto launch = [&](int stream, int kind, int conv, const char* kernel) -> clasfv_plan_launch_t& {
+      clasfv_plan_launch_t l{};
+      l.sub_batch = sub, l.stream = stream, l.kind = kind, l.conv = conv, l.kernel = kernel;
+      l.split_asked = l.split_granted = 1;
+      l.x_elem = l.y_elem = 4;
+      rec.launches.push_back(l);
+      return rec.launches.back();
+    };
+    auto add = [&](clasfv_plan_launch_t& l, int buffer, int role, int write, int64_t offset, int64_t bytes) {
+      if (l.n_ranges < CLASFV_PLAN_MAX_RANGES) l.range[l.n_ranges++] = {buffer, role, write, 0, offset, bytes};
+    };
+    // a range of the arena: the buffer is the one its first byte lies in
+    auto add_arena = [&](clasfv_plan_launch_t& l, const void* p, int role, int write, int64_t bytes) {
+      const int64_t off = reinterpret_cast<const char*>(p) - arena;
+      int b = 0;
+      while (b + 1 < NBUF && off >= (int64_t)L.off[b + 1]) ++b;
+      add(l, b, role, write, off, bytes);
+    };
+    const CallerOffsets at = caller_offsets(n0, T, H, W);
+    const int64_t clip = (int64_t)T * H * W;
+    auto pack = [&](void* xin) {
+      clasfv_plan_launch_t& l = launch(0, CLASFV_PLAN_PACK, -1, "pack_input_kernel");
+      add(l, CLASFV_PLAN_EXT_CLIP, CLASFV_PLAN_X, 0, (int64_t)at.x * 4, (int64_t)n * 3 * clip * 4);
+      add_arena(l, xin, CLASFV_PLAN_Y, 1, (int64_t)n * clip * 4 * 4);  // launch_pack_input: 3 + 1 fp32 channels
+      return (int)CLASFV_OK;
+    };
+    auto conv = [&](int stream, const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res,
+                    bool relu, const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
+      const KernelInfo* k = nullptr;
+      ConvBuilt cb{};
+      if (int rc = run_conv(c, xin, in, y, out, res, relu, nullptr, arena, x2, &k, h->tune, x_c8, y_c8, scratch,
+                            scratch_bytes, true, &cb))
+        return rc;
+      const ConvParams& p = cb.p;
+      const int xe = p.in_bf16 ? 2 : 4, ye = p.out_bf16 ? 2 : 4;
+      const int64_t vin = (int64_t)p.N * p.Ti * p.Hi * p.Wi, m = (int64_t)p.N * p.To * p.Ho * p.Wo;
+      const int64_t part = (int64_t)p.n_split * m * p.Cout * 4;
+      const bool split = p.n_split > 1;
+      clasfv_plan_launch_t& l = launch(stream, CLASFV_PLAN_CONV, conv_index(h, c), k->name);
+      auto describe = [&](clasfv_plan_launch_t& d) {
+        d.split_asked = cb.split_asked, d.split_granted = split ? p.n_split : 1;
+        d.x_c8 = p.x_c8, d.y_c8 = p.y_c8, d.relu = p.relu, d.has_res = p.res != nullptr;
+        d.x_elem = xe, d.y_elem = ye;
+      };
+      auto epilogue = [&](clasfv_plan_launch_t& d) {  // what the launch that writes y addresses beside its sums
+        if (p.res) add_arena(d, p.res, CLASFV_PLAN_RES, 0, m * p.Cout * ye);
+        add_arena(d, p.y, CLASFV_PLAN_Y, 1, m * p.Cout * ye);
+      };
+      describe(l);
+      add_arena(l, p.x, CLASFV_PLAN_X, 0, vin * p.Cin * xe);
+      if (p.x2) add_arena(l, p.x2, CLASFV_PLAN_X2, 0, vin * p.Cin2 * xe);
+      if (!split) {
+        epilogue(l);
+        return (int)CLASFV_OK;
+      }
+      add_arena(l, p.part, CLASFV_PLAN_PART, 1, part);
+      clasfv_plan_launch_t& ssum = launch(stream, CLASFV_PLAN_SPLIT_SUM, conv_index(h, c), "split_sum_kernel");
+      describe(ssum);
+      add_arena(ssum, p.part, CLASFV_PLAN_PART, 0, part);
+      epilogue(ssum);
+      return (int)CLASFV_OK;
+    };
+    auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
+                   const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
+      return conv(0, c, xin, in, y, out, res, relu, x2, x_c8, y_c8, scratch, scratch_bytes);
+    };
+    auto run_side = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* x2) {
+      launch(1, CLASFV_PLAN_FORK, -1, "");  // ev_fork recorded on s, awaited by the side stream
+      side_pending = true;
+      return conv(1, c, xin, in, y, out, nullptr, false, x2, 0, 0, nullptr, 0);
+    };
+    auto join = [&]() {
+      if (side_pending) launch(0, CLASFV_PLAN_JOIN, -1, "");  // ev_join recorded on the side stream, awaited by s
+      side_pending = false;
+      return (int)CLASFV_OK;
+    };
+    auto decode = [&](const float* const tp[4], const Shape5 tsh[4], void* idx) {
+      const DecParams d = decoder_params(h, tp, tsh, nullptr, nullptr, n, T, H, W, idx);
+      if (!decoder_addressable(d)) return fail(CLASFV_EBADSHAPE, "decoder_kernel: a tap has 2^31 floats or more");
+      const int64_t table = (int64_t)decoder_index_bytes(d.T, d.H, d.W);
+      clasfv_plan_launch_t& li = launch(0, CLASFV_PLAN_DEC_INDEX, -1, "decoder_index_kernel");
+      add_arena(li, d.idx, CLASFV_PLAN_IDX, 1, table);
+      clasfv_plan_launch_t& l = launch(0, CLASFV_PLAN_DECODER, -1, "decoder_kernel");
+      for (int i = 0; i < 4; ++i)
+        add_arena(l, d.tap[i].p, CLASFV_PLAN_TAP, 0, (int64_t)d.N * d.tap[i].T * d.tap[i].H * d.tap[i].W * 64 * 4);
+      add_arena(l, d.idx, CLASFV_PLAN_IDX, 0, table);
+      add(l, CLASFV_PLAN_EXT_SEG, CLASFV_PLAN_Y, 1, (int64_t)at.seg * 4, (int64_t)d.N * 2 * clip * 4);
+      add(l, CLASFV_PLAN_EXT_MOTION, CLASFV_PLAN_Y, 1, (int64_t)at.mot * 4, (int64_t)d.N * 4 * clip * 4);
+      return (int)CLASFV_OK;
+    };
+    return walk_network(h, L, arena, n, T, H, W, pack, run, run_side, join, decode);
+  });
 }
 
 }  // namespace
@@ -1392,6 +1557,33 @@ int clasfv_clips_fit(int N, int T, int H, int W, int dtype, int variants) {
   return forward_fits(&e, N, T, H, W);
 }
 
+int clasfv_forward_plan(int N, int T, int H, int W, int dtype, int variants, int cap_launches,
+                        clasfv_plan_launch_t* launches, int* n_launches, int cap_buffers, clasfv_plan_buffer_t* buffers,
+                        int* n_buffers) {
+  if (N < 1) return fail(CLASFV_EINVAL, "N must be >= 1");
+  if (cap_launches < 0 || cap_buffers < 0) return fail(CLASFV_EINVAL, "negative cap");
+  clasfv_engine e;
+  if (int rc = plan_only(&e, T, H, W, dtype, variants)) return rc;
+  PlanRecorder rec;
+  if (int rc = forward_plan(&e, N, T, H, W, rec)) return rc;
+  if (n_launches) *n_launches = (int)rec.launches.size();
+  if (n_buffers) *n_buffers = (int)rec.buffers.size();
+  if ((launches && rec.launches.size() > (size_t)cap_launches) || (buffers && rec.buffers.size() > (size_t)cap_buffers))
+    return fail(CLASFV_EINVAL, "forward plan: cap too small");
+  if (launches) std::copy(rec.launches.begin(), rec.launches.end(), launches);
+  if (buffers) std::copy(rec.buffers.begin(), rec.buffers.end(), buffers);
+  return CLASFV_OK;
+}
+
+int clasfv_plan_conv_info(int dtype, int i, int channels[5], int kernel[3], int stride[3], int padding[3],
+                          int* in_dtype, int* out_dtype) {
+  if (dtype != CLASFV_DTYPE_FP32 && dtype != CLASFV_DTYPE_BF16) return fail(CLASFV_EINVAL, "unknown dtype");
+  clasfv_engine e;
+  e.dtype = dtype;
+  build_plan(&e);
+  return clasfv_conv_info(&e, i, nullptr, nullptr, nullptr, channels, kernel, stride, padding, in_dtype, out_dtype);
+}
+
 int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float* seg, float* mot, void* stream) {
   if (!h) return fail(CLASFV_EINVAL, "null handle");
   if (!h->ready) return fail(CLASFV_ENOTREADY, "clasfv_finalize has not been called");
@@ -1472,13 +1664,10 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     HIP_TRY(side_join.join());
     return (int)CLASFV_OK;
   };
-  for (int n0 = 0; n0 < N; n0 += nb) {
-    const int n = std::min(nb, N - n0);
-    // the last, shorter sub-batch runs in the layout of a forward of its own size (it fits the arena)
-    if (n != nb) make_layout(n, T, H, W, L);
-    const size_t clip = (size_t)T * H * W;
-    const float* xs = x + (size_t)n0 * 3 * clip;
-    float *segs = seg + (size_t)n0 * 2 * clip, *mots = mot + (size_t)n0 * 4 * clip;
+  return for_sub_batches(N, nb, T, H, W, [&](int, int n0, int n, const Layout& Ls) {
+    const CallerOffsets at = caller_offsets(n0, T, H, W);
+    const float* xs = x + at.x;
+    float *segs = seg + at.seg, *mots = mot + at.mot;
     auto pack = [&](void* xin) {
       log_begin(h);
       HIP_TRY(launch_pack_input(xs, reinterpret_cast<float*>(xin), n, T, H * W, s));
@@ -1500,9 +1689,8 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
             2.0 * n * (double)T * H * W * dec_px * 1e-9);
       return (int)CLASFV_OK;
     };
-    if (int rc = walk_network(h, L, cx->arena, n, T, H, W, pack, run, run_side, join, decode)) return rc;
-  }
-  return CLASFV_OK;
+    return walk_network(h, Ls, cx->arena, n, T, H, W, pack, run, run_side, join, decode);
+  });
 }
 
 int clasfv_set_kernel_timing(clasfv_t h, int enable) {
@@ -1573,6 +1761,17 @@ int clasfv_fill_workspace(clasfv_t h, int byte, void* stream) {
   if (!cx || !cx->arena) return fail(CLASFV_EINVAL, "no workspace exists for this stream yet");
   DEVICE_GUARD(h->device);
   HIP_TRY(hipMemsetAsync(cx->arena, byte, cx->arena_bytes, s));
+  return CLASFV_OK;
+}
+
+int clasfv_workspace_view(clasfv_t h, void* stream, void** base, int64_t* bytes) {
+  if (!h) return fail(CLASFV_EINVAL, "null handle");
+  const clasfv_engine::Ctx* cx = nullptr;
+  for (const auto* c : h->ctxs)
+    if (c->stream == (hipStream_t)stream) cx = c;
+  if (!cx || !cx->arena) return fail(CLASFV_EINVAL, "no workspace exists for this stream yet");
+  if (base) *base = cx->arena;
+  if (bytes) *bytes = (int64_t)cx->arena_bytes;
   return CLASFV_OK;
 }
 

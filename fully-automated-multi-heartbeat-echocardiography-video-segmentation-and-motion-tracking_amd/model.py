@@ -27,6 +27,61 @@ from .arch import strip_module_prefix
 from .weights import DEFAULT_SEED, recipe_state_dict
 
 
+def variant_flags(names):
+    """CLASFV_VARIANT_* bits of variant names (an int passes through)."""
+    if isinstance(names, int):
+        return names
+    flags = 0
+    for n in names:
+        if n not in _lib.VARIANTS:
+            raise ValueError(f"unknown kernel variant {n!r}: {sorted(_lib.VARIANTS)}")
+        flags |= _lib.VARIANTS[n]
+    return flags
+
+
+def forward_plan(n, t, h, w, dtype="fp32", variants=()):
+    """clasfv_forward_plan: what a forward of n clips of (t, h, w) issues on an engine of `dtype` and `variants`
+    (names or bits), as {"launches": [...], "buffers": [...]}; host arithmetic, needs no GPU. A launch is a
+    dict of clasfv_plan_launch_t's fields with "kind" and each range's "role" as their names (_lib.PLAN_KINDS,
+    _lib.PLAN_ROLES) and "ranges" a list of {"buffer", "role", "write", "offset", "bytes"}; a buffer row a dict
+    of clasfv_plan_buffer_t's."""
+    lib = _lib.load()
+    args = (n, t, h, w, _lib.DTYPES[dtype], variant_flags(variants))
+    nl, nbuf = ctypes.c_int(), ctypes.c_int()
+    _lib.check(lib.clasfv_forward_plan(*args, 0, None, ctypes.byref(nl), 0, None, ctypes.byref(nbuf)), "clasfv_forward_plan")
+    launches, buffers = (_lib.PlanLaunch * nl.value)(), (_lib.PlanBuffer * nbuf.value)()
+    _lib.check(lib.clasfv_forward_plan(*args, nl.value, launches, ctypes.byref(nl), nbuf.value, buffers,
+                                       ctypes.byref(nbuf)), "clasfv_forward_plan")
+    scalars = ("sub_batch", "stream", "conv", "split_asked", "split_granted", "x_c8", "y_c8", "relu", "has_res",
+               "x_elem", "y_elem")
+    out = []
+    for l in launches:
+        d = {k: int(getattr(l, k)) for k in scalars}
+        d["kind"] = _lib.PLAN_KINDS[l.kind]
+        d["kernel"] = l.kernel.decode()
+        d["ranges"] = [{"buffer": int(r.buffer), "role": _lib.PLAN_ROLES[r.role], "write": bool(r.write),
+                        "offset": int(r.offset), "bytes": int(r.bytes)} for r in l.range[:l.n_ranges]]
+        out.append(d)
+    rows = [{"sub_batch": int(b.sub_batch), "clips": int(b.clips), "id": int(b.id), "name": b.name.decode(),
+             "offset": int(b.offset), "bytes": int(b.bytes), "total": int(b.total)} for b in buffers]
+    return {"launches": out, "buffers": rows}
+
+
+def plan_conv_table(dtype="fp32"):
+    """Engine.conv_table()'s channels, kernel, stride, padding and dtypes for an engine of `dtype`, without a
+    handle (clasfv_plan_conv_info): one dict per conv, the backbone in execution order, then P01, P2, P3, P4."""
+    lib = _lib.load()
+    out = []
+    din, dout = ctypes.c_int(), ctypes.c_int()
+    ch, k, s, p = (ctypes.c_int * 5)(), (ctypes.c_int * 3)(), (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    while lib.clasfv_plan_conv_info(_lib.DTYPES[dtype], len(out), ch, k, s, p, ctypes.byref(din), ctypes.byref(dout)) == 0:
+        out.append({"index": len(out), "cin": ch[0], "cout": ch[1], "cin_p": ch[2], "cout_p": ch[3], "cin2": ch[4],
+                    "kernel": tuple(k), "stride": tuple(s), "padding": tuple(p),
+                    "in_dtype": torch.bfloat16 if din.value == 1 else torch.float32,
+                    "out_dtype": torch.bfloat16 if dout.value == 1 else torch.float32})
+    return out
+
+
 class Engine:
     """Owns one clasfv handle (weights + workspace) on one HIP device."""
 
@@ -175,6 +230,17 @@ class Engine:
         """Fill the whole workspace arena of `stream`'s context with `byte` (clasfv_fill_workspace; tests)."""
         _lib.check(self.lib.clasfv_fill_workspace(self.h, int(byte), _lib.stream_ptr(stream, self.device)),
                    "clasfv_fill_workspace")
+
+    def workspace_view(self, stream=None):
+        """(device address, bytes) of the arena of `stream`'s context (clasfv_workspace_view; tests)."""
+        base, size = ctypes.c_void_p(), ctypes.c_int64()
+        _lib.check(self.lib.clasfv_workspace_view(self.h, _lib.stream_ptr(stream, self.device), ctypes.byref(base),
+                                                  ctypes.byref(size)), "clasfv_workspace_view")
+        return int(base.value), int(size.value)
+
+    def forward_plan(self, n, t, h, w):
+        """forward_plan() of n clips of (t, h, w) for this engine's dtype and variants."""
+        return forward_plan(n, t, h, w, self.dtype, self.lib.clasfv_get_kernel_variants(self.h))
 
 
 class R2plus1D_18_MotionNet(nn.Module):

@@ -183,6 +183,86 @@ int clasfv_launch_log(clasfv_t h, int cap, const char** labels, int64_t* grids, 
  * (0xFF in every byte is a NaN in fp32 and in bf16). CLASFV_EINVAL for a null handle, a byte outside
  * [0, 255], or a stream no clasfv_forward / clasfv_run_decoder has created a context for yet. */
 int clasfv_fill_workspace(clasfv_t h, int byte, void* stream);
+/* The arena of the context that belongs to `stream`: its device address in *base_dev and its size in
+ * *bytes (either may be NULL). The arena is the library's: read it, after synchronising the stream, and
+ * write it only through clasfv_fill_workspace; the address holds until a forward of a larger shape on
+ * the stream, or a fifth stream, replaces the arena. For tests that compare what a forward wrote with
+ * clasfv_forward_plan. CLASFV_EINVAL as clasfv_fill_workspace: a null handle, or a stream without a
+ * context. */
+int clasfv_workspace_view(clasfv_t h, void* stream, void** base_dev, int64_t* bytes);
+
+/* ---- diagnostics: the launch plan (new exports only: the ABI revision is unchanged) ----------- */
+/* What clasfv_forward issues for N clips of (T, H, W) on an engine of compute dtype `dtype` and kernel
+ * variants `variants`, recorded by the forward's own walk of the network (the same sub-batch loop, the
+ * same layout, the same kernel choice and split-K rule, with nothing launched): every launch in issue
+ * order with the memory it reads and writes, the fork and join events of the side stream as markers,
+ * and the buffers of each sub-batch's arena layout. Host arithmetic only: needs neither a handle nor a
+ * device. DESIGN.md, "The arena's contract", states what a plan must satisfy; tests/plan_audit.py
+ * checks it. */
+enum {
+  CLASFV_PLAN_PACK = 0,       /* pack_input_kernel: the clip into XIN */
+  CLASFV_PLAN_CONV = 1,       /* a conv kernel (with a split granted it writes partial sums, not y) */
+  CLASFV_PLAN_SPLIT_SUM = 2,  /* split_sum_kernel: the partial sums, bias, residual and ReLU into y */
+  CLASFV_PLAN_DEC_INDEX = 3,  /* decoder_index_kernel: the decoder's source-index table */
+  CLASFV_PLAN_DECODER = 4,    /* decoder_kernel */
+  CLASFV_PLAN_FORK = 5,       /* marker: the side stream waits for everything issued on the caller's so far */
+  CLASFV_PLAN_JOIN = 6        /* marker: the caller's stream waits for everything issued on the side stream so far */
+};
+/* What a range is to its launch. */
+enum {
+  CLASFV_PLAN_X = 0,     /* the conv's input, x_elem bytes per element */
+  CLASFV_PLAN_X2 = 1,    /* the second input of the dual projection, x_elem */
+  CLASFV_PLAN_RES = 2,   /* the residual, y_elem */
+  CLASFV_PLAN_Y = 3,     /* the output, y_elem */
+  CLASFV_PLAN_PART = 4,  /* split-K partial sums, fp32 */
+  CLASFV_PLAN_IDX = 5,   /* the decoder's index table, 16-byte entries */
+  CLASFV_PLAN_TAP = 6    /* a projected tap the decoder reads, fp32 */
+};
+/* Buffer ids of the caller's tensors; offsets are bytes from the tensor's start. The arena's buffers
+ * have the ids 0 .. of clasfv_plan_buffer_t. */
+enum { CLASFV_PLAN_EXT_CLIP = -1, CLASFV_PLAN_EXT_SEG = -2, CLASFV_PLAN_EXT_MOTION = -3 };
+#define CLASFV_PLAN_MAX_RANGES 8
+typedef struct clasfv_plan_range {
+  int32_t buffer; /* arena buffer id, or CLASFV_PLAN_EXT_* */
+  int32_t role;   /* CLASFV_PLAN_X .. */
+  int32_t write;  /* 1: written, 0: read */
+  int32_t pad_;
+  int64_t offset; /* bytes from the arena's base (from the tensor's start for CLASFV_PLAN_EXT_*) */
+  int64_t bytes;
+} clasfv_plan_range_t;
+typedef struct clasfv_plan_launch {
+  int32_t sub_batch;    /* index of the sub-batch of the call */
+  int32_t stream;       /* 0: the caller's stream, 1: the side stream */
+  int32_t kind;         /* CLASFV_PLAN_PACK .. */
+  int32_t conv;         /* clasfv_conv_info's index as the launch log reports it, or -1 */
+  const char* kernel;   /* static string: the kernel's name as clasfv_kernel_timing reports it ("" for a marker) */
+  int32_t split_asked;  /* split-K factor the per-clip rule asks for (1: none) */
+  int32_t split_granted; /* the factor the launch runs with */
+  int32_t x_c8, y_c8, relu, has_res;
+  int32_t x_elem, y_elem; /* bytes per element of the input and of the output */
+  int32_t n_ranges, pad_;
+  clasfv_plan_range_t range[CLASFV_PLAN_MAX_RANGES];
+} clasfv_plan_launch_t;
+typedef struct clasfv_plan_buffer {
+  int32_t sub_batch;   /* the layout is per sub-batch: a shorter last one has its own */
+  int32_t clips;       /* clips of the sub-batch */
+  int32_t id;          /* 0 ..: XIN, S0, X0, MID, TA, DSB, L1A, L1, ... P01, PP2, PP3, PP4, DIDX */
+  int32_t pad_;
+  const char* name;    /* static string */
+  int64_t offset, bytes; /* of the buffer in the arena; bytes includes no slack */
+  int64_t total;       /* bytes of the sub-batch's whole layout; the first one's is the arena clasfv_forward allocates */
+} clasfv_plan_buffer_t;
+/* Writes up to cap_launches launches and cap_buffers buffer rows and the counts there are in *n_launches
+ * and *n_buffers (any pointer may be NULL with its cap 0: call once to size, once to fill). CLASFV_EINVAL
+ * for N < 1, an unknown dtype or variant bit, or a cap smaller than the count when its array is given;
+ * CLASFV_EBADSHAPE as clasfv_forward. */
+int clasfv_forward_plan(int N, int T, int H, int W, int dtype, int variants, int cap_launches,
+                        clasfv_plan_launch_t* launches, int* n_launches, int cap_buffers,
+                        clasfv_plan_buffer_t* buffers, int* n_buffers);
+/* Conv i of an engine of compute dtype `dtype`, as clasfv_conv_info reports it for a handle of that
+ * dtype (prefixes and tap omitted), without a handle or a device. */
+int clasfv_plan_conv_info(int dtype, int i, int channels[5], int kernel[3], int stride[3], int padding[3],
+                          int* in_dtype, int* out_dtype);
 
 /* ---- diagnostics: one layer alone (for layer-level tests; not on the reference's interface) - */
 /* New exports only: the ABI revision is unchanged. Convs are numbered in execution order: the

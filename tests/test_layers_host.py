@@ -123,28 +123,59 @@ def test_fill_workspace_rejects_a_null_handle():
 
 
 # ---- size limits: max_clips and the gates behind it (host arithmetic, no device) ---------------------------
-LIM31 = 1 << 31
+LIM31, LIM32 = 1 << 31, 1 << 32
 
 
 def _closed_form(dtype, t, h, w):
-    """The limit that binds at the network's shapes, by DESIGN.md's "Size limits" table. fp32: the 64-channel
-    fp32 input of layer1's F(4x4,3x3) convs, (t, h/2, w/2), ends below byte 2^31 (the kernels' "read zeros"
-    slot). bf16: the decoder's P01 tap, 64 fp32 channels at (t, h/2, w/2), has fewer than 2^31 floats."""
+    """The limit that binds at the network's shapes, by DESIGN.md's "Size limits" table. fp32: layer1's
+    144-channel fp32 mid tensor, (t, h/2, w/2), 8-channel-blocked for conv_winot5, which offsets it in 32-bit
+    bytes, stays below 2^32 bytes (the blocked layout is one clip's choice: a batch does not switch it off).
+    That is below the limit the F(4x4,3x3) convs set on their 64-channel input, 2^31 bytes (the kernels'
+    "read zeros" slot), which bound the forward while a batch could. bf16: layer1's 160-channel bf16 mid
+    tensor, (t, h/2, w/2), has fewer than the 2^31 elements conv_twalk_bf16 addresses. (This export used to
+    answer with the decoder's limit, 2^31 floats in the P01 tap, 2.5 times as many clips: its device-less
+    engine marked no bias present, so its bf16 convs were planned on other kernels than a finalized handle
+    runs, whose forward has always used the limit asserted here.)"""
     vox = t * (h // 2) * (w // 2)
-    return (LIM31 - 1) // (vox * 64 * 4) if dtype == 0 else (LIM31 - 1) // (vox * 64)
+    assert (LIM32 - 1) // (vox * 144 * 4) <= (LIM31 - 1) // (vox * 64 * 4)
+    return (LIM32 - 1) // (vox * 144 * 4) if dtype == 0 else (LIM31 - 1) // (vox * 160)
+
+
+def _dma_w_bound(t, h, w):
+    """The 64-channel bf16 input of layer2's first conv, (t, h/2, w/2), from one padding row and pixel (w/2 + 1
+    pixels) before it, stays below the 2^31 bytes conv_dma_w's buffer DMAs address (conv_dma would take a
+    larger batch, bit for bit the same, but a batch does not change a clip's kernel)."""
+    return ((LIM31 - 1) // (64 * 2) - (w // 2 + 1)) // (t * (h // 2) * (w // 2))
+
+
+def _decoder_bound(t, h, w):
+    return (LIM31 - 1) // (t * (h // 2) * (w // 2) * 64)
 
 
 def test_max_clips_at_the_product_shapes_and_which_limit_binds():
     from clasfv_amd import _lib
     lib = _lib.load()
-    want = {(0, 64, 224, 224): 10, (0, 32, 112, 112): 83, (1, 64, 224, 224): 41, (1, 32, 112, 112): 334}
+    want = {(0, 64, 224, 224): 9, (0, 32, 112, 112): 74, (1, 64, 224, 224): 16, (1, 32, 112, 112): 133}
     for (dtype, t, h, w), n in want.items():
         assert _closed_form(dtype, t, h, w) == n
         assert lib.clasfv_max_clips(t, h, w, dtype, 0) == n
         assert lib.clasfv_clips_fit(n, t, h, w, dtype, 0) == 0
         assert lib.clasfv_clips_fit(n + 1, t, h, w, dtype, 0) == -2
         msg = lib.clasfv_last_error()
-        assert (b"conv_wino4r" if dtype == 0 else b"decoder_kernel") in msg, msg
+        assert (b"conv_winot: the 8-channel-blocked input" if dtype == 0 else b"conv_twalk_bf16: the batch is past") in msg, msg
+    # channels-last mid tensors (no_c8): the F(4x4,3x3) convs' 64-channel input below 2^31 bytes binds instead
+    for (t, h, w), n in {(64, 224, 224): 10, (32, 112, 112): 83}.items():
+        no_c8 = _lib.VARIANTS["no_c8"]
+        assert lib.clasfv_max_clips(t, h, w, 0, no_c8) == n == (LIM31 - 1) // (t * (h // 2) * (w // 2) * 64 * 4)
+        assert lib.clasfv_clips_fit(n + 1, t, h, w, 0, no_c8) == -2 and b"conv_wino4r" in lib.clasfv_last_error()
+    # bf16 without conv_twalk_bf16: conv_dma_w's 2^31 bytes bind; without conv_dma_w too, the decoder's P01 tap
+    no_twalk, no_dma_w = _lib.VARIANTS["no_twalk"], _lib.VARIANTS["no_dma_w"]
+    for (t, h, w), (n_w, n_dec) in {(64, 224, 224): (20, 41), (32, 112, 112): (167, 334)}.items():
+        assert lib.clasfv_max_clips(t, h, w, 1, no_twalk) == n_w == _dma_w_bound(t, h, w)
+        assert lib.clasfv_clips_fit(n_w + 1, t, h, w, 1, no_twalk) == -2 and b"conv_dma_w" in lib.clasfv_last_error()
+        assert lib.clasfv_max_clips(t, h, w, 1, no_twalk | no_dma_w) == n_dec == _decoder_bound(t, h, w)
+        assert lib.clasfv_clips_fit(n_dec + 1, t, h, w, 1, no_twalk | no_dma_w) == -2
+        assert b"decoder_kernel" in lib.clasfv_last_error()
     # other clips whose layer1 maps F(4x4,3x3) serves: the same closed forms
     for t, h, w in ((8, 32, 48), (16, 80, 112), (24, 64, 64)):
         for dtype in (0, 1):
@@ -164,7 +195,7 @@ def test_clips_fit_is_monotone_in_the_batch():
                             (1, V["no_patch_bf16"]), (1, V["no_twalk"] | V["no_dma_w"])):
         t, h, w = 32, 112, 112
         mc = lib.clasfv_max_clips(t, h, w, dtype, variants)
-        assert 1 <= mc <= _closed_form(1, t, h, w)  # the decoder's tap bounds every configuration
+        assert 1 <= mc <= _decoder_bound(t, h, w)  # the decoder's tap bounds every configuration
         fits = [lib.clasfv_clips_fit(n, t, h, w, dtype, variants) == 0
                 for n in (1, 2, mc // 2, mc - 1, mc, mc + 1, mc + 2, 2 * mc, 10 * mc, LIM31 // (t * h * w) + 5)]
         assert fits == [True] * 5 + [False] * 5, (dtype, variants, mc, fits)
