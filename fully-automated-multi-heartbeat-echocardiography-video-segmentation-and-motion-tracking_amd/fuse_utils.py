@@ -98,7 +98,11 @@ _TABLES = {}
 
 def _device_table(table, device):
     """Device int32 copy of a clip table, cached: a fresh pageable host->device copy per call would
-    make every video wait for the copy engine (and the host for the stream) before its clips build."""
+    make every video wait for the copy engine (and the host for the stream) before its clips build.
+    A table is allocated on the stream that first asked for it and read by kernels on every stream that
+    asks later, so each hand-out records the current stream on it: when the cache is emptied, the
+    allocator keeps the block until the work queued on those streams so far has run (without that, a new
+    tensor could take the block while a kernel that has not started yet still reads the table)."""
     key = (str(device), tuple(table))
     t = _TABLES.get(key)
     if t is None:
@@ -106,6 +110,7 @@ def _device_table(table, device):
             _TABLES.clear()
         t = torch.tensor(np.asarray(table, np.int32).reshape(-1), device=device)
         _TABLES[key] = t
+    t.record_stream(torch.cuda.current_stream(t.device))
     return t
 
 
