@@ -291,7 +291,15 @@ def case_id(c):
 
 
 # ---- models -----------------------------------------------------------------------------------------
+RESCALE_K = 30  # per-channel exponents of the "rescaled" kind: uniform in [-30, 30]
+
+
 class Net:
+    """An engine of `dtype` loaded with a recipe of oracle/layer_ref.py. kind: "int" (integer_state_dict),
+    "float" (float_state_dict), "rescaled" (the float recipe after rescale_state_dict: the same function with
+    channels spread over 2^+-RESCALE_K, "rescaled<K>" over another range; self.exps its exponent vectors) or
+    "spread" (spread_state_dict)."""
+
     def __init__(self, dtype, kind):
         from clasfv_amd.model import R2plus1D_18_MotionNet
         self.model = R2plus1D_18_MotionNet(pretrained=False, dtype=dtype)
@@ -299,16 +307,19 @@ class Net:
         if kind == "int":
             self.sd, self.ks = LR.integer_state_dict(table, seed=11)
         else:
-            self.sd = LR.float_state_dict(table, seed=12)
+            self.sd = (LR.spread_state_dict if kind == "spread" else LR.float_state_dict)(table, seed=12)
             # heads for the decoder test: keep comb_2's sums and tanh's argument of order 1
             self.sd["comb_2_layer.weight"] *= 0.125
             self.sd["segmentation_head.weight"] *= 0.125
             self.sd["motion_head.weight"] *= 0.0625
             for e in self.model.engine.conv_table():
-                if e["tap"] < 0 and e["prefix"][len(R):] in RELU_ONLY[dtype]:
+                # (the spread recipe's gammas have random signs: about half the outputs are positive as drawn)
+                if kind != "spread" and e["tap"] < 0 and e["prefix"][len(R):] in RELU_ONLY[dtype]:
                     scale, _ = LR.bn_fold(self.sd, e["bn"])
                     k = e["cin"] * e["kernel"][0] * e["kernel"][1] * e["kernel"][2]
                     self.sd[e["bn"] + ".bias"] += (2.0 * (k * (7 / 12) ** 2) ** 0.5 * scale.abs()).float()
+        if kind.startswith("rescaled"):  # the float recipe, every channel moved by its own power of two (same function)
+            self.sd, self.exps = LR.rescale_state_dict(self.sd, int(kind[len("rescaled"):] or RESCALE_K), seed=13)
         self.model.load_state_dict(self.sd)
         self.engine = self.model.engine
         self.dtype, self.kind = dtype, kind
@@ -366,14 +377,20 @@ def guards_intact(bits):
 COL0 = {"P01": 0, "P2": 128, "P3": 256, "P4": 512}
 
 
-def build_case(nt, c):
-    """Inputs in the engine's layouts and the float64 pre-activation reference of one case."""
+def build_case(nt, c, per_element=False, reference=True):
+    """Inputs in the engine's layouts and the float64 pre-activation reference of one case (reference=False:
+    the inputs only, for checks that compare two runs). The "spread" kind draws LR.spread_draw activations
+    (per_element: an exponent per element instead of one per (n, c))."""
     e = nt.by_name[c["layer"]]
     kind, sd = nt.kind, nt.sd
     gen = torch.Generator().manual_seed(sum(map(ord, case_id(c))))
     n, t, h, w = c["nthw"]
-    draw = (lambda shape: torch.randint(-2, 3, shape, generator=gen).double()) if kind == "int" else \
-        (lambda shape: LR.signed_unit(shape, gen, torch.float64))
+    if kind == "int":
+        draw = lambda shape: torch.randint(-2, 3, shape, generator=gen).double()
+    elif kind == "spread":
+        draw = LR.spread_draw(gen, per_element=per_element)
+    else:
+        draw = lambda shape: LR.signed_unit(shape, gen, torch.float64)
     bf_in, bf_out = e["in_dtype"] == torch.bfloat16, e["out_dtype"] == torch.bfloat16
     cin_all = e["cin"] + e["cin2"]
     x = draw((n, cin_all, t, h, w))
@@ -387,7 +404,10 @@ def build_case(nt, c):
     chans = None
     if c["sub"]:
         chans = torch.tensor([16 * i + j for i in range(e["cout"] // 16) for j in (3, 12)])
-    if e["tap"] >= 0:  # a column block of comb_1 with BN1's scale, no bias
+    y = den = wf = shift = None
+    if not reference:
+        pass
+    elif e["tap"] >= 0:  # a column block of comb_1 with BN1's scale, no bias
         scale, _ = LR.bn_fold(sd, "comb_batch_norm_1")
         o0 = COL0[c["layer"]]
         w_raw = sd["comb_1_layer.weight"].double()[:, o0:o0 + cin_all]
@@ -420,8 +440,13 @@ def build_case(nt, c):
     if res is not None:
         res_dev, rec = guarded_input(LR.to_channels_last(res, e["cout_p"], e["out_dtype"]), dev)
         records.append(rec)
+    # x64, res64, wf, shift: the operands on the CPU (wf, shift: of `chans` where set), for emulations of a kernel's
+    # designed arithmetic (oracle/layer_ref.py)
     return dict(e=e, x=x_dev, x2=x2_dev, res=res_dev, inputs=records, y64=y, den=den, out=(n, to_, ho, wo), chans=chans,
-                xmin=float(x.abs()[x != 0].min()) if x.numel() else 0.0, wfmin=float(wf.abs()[wf != 0].min()))
+                x64=x, res64=res if chans is None or res is None else res[:, chans], wf=wf,
+                shift=shift if chans is None or shift is None else shift[chans],
+                xmin=float(x.abs()[x != 0].min()) if x.numel() else 0.0,
+                wfmin=float(wf.abs()[wf != 0].min()) if reference else None)
 
 
 def launch(nt, c, b, relu, alias=False):
