@@ -136,7 +136,10 @@ struct DecParams {
 // bytes of DecParams::idx: per tap, T frame + H row + W column entries of 16 B
 inline size_t decoder_index_bytes(int T, int H, int W) { return (size_t)4 * (T + H + W) * 16; }
 
-// Launchers (stream-ordered, no synchronisation). Return hipError_t of the launch.
+// Launchers (stream-ordered, no synchronisation). Return hipError_t of the launch. A *_supported gate says
+// whether its kernel can run these parameters; the variant bits that switch a whole kernel off are not read
+// here but named by the kernel's row of engine.hip's kKernels (`off`). A gate reads p.vflags only for a bit
+// that chooses a form inside its launcher, which re-asks the gate (dma_w_ok: no_dma_w, no_dma_buf).
 hipError_t launch_conv(const ConvParams& p, int mt, int bn, hipStream_t s);
 // Block tile (BM = 64*mt rows, bn output channels) for an M x cout_p conv.
 void conv_pick_tile(int M, int cout_p, int force_nt, int* mt, int* bn);

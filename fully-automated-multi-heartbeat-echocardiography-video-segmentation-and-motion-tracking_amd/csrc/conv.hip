@@ -1512,9 +1512,8 @@ hipError_t launch_dma_bf16_ko(const ConvParams& p, int bn, int ko, hipStream_t s
 // conv_proj_x3: fp32 1x1x1 stride-1 convs to 64 channels over K = Cin (+ Cin2) = 128, both inputs
 // multiples of 32 channels, channels-last in and out, no split-K (the decoder projections P01 and P2;
 // K = 256 (P3) needs more registers than the item ring leaves and stays on conv_dma_x3). A split-bf16
-// kernel: the no_dma_x3 variant (every non-stem GEMM on f32 MFMAs) excludes it too.
+// kernel: the no_dma_x3 variant (every non-stem GEMM on f32 MFMAs) excludes it too (engine.hip, kKernels).
 bool proj_x3_supported(const ConvParams& p) {
-  if (p.vflags & CLASFV_VARIANT_NO_DMA_X3) return false;
   if (p.in_bf16 || p.out_bf16 || p.stem || p.x_c8 || p.y_c8 || p.n_split > 1) return false;
   if (p.KT != 1 || p.KH != 1 || p.KW != 1 || p.st != 1 || p.sh != 1 || p.sw != 1) return false;
   if (p.Cout != 64 || p.Cin % 32 || (p.x2 && p.Cin2 % 32)) return false;
@@ -1540,8 +1539,8 @@ hipError_t launch_proj_x3(const ConvParams& p, hipStream_t s) {
 
 // conv_dma_x3 (fp32 engines, non-stem implicit-GEMM convs): fp32 activations in, fp32 out
 bool dma_x3_supported(const ConvParams& p) {
-  return !(p.vflags & CLASFV_VARIANT_NO_DMA_X3) && !p.in_bf16 && !p.out_bf16 && !p.stem && !p.x_c8 && !p.y_c8 &&
-         p.Kp % 16 == 0 && p.Cin % 16 == 0 && (!p.x2 || p.Cin2 % 16 == 0) && p.Cout % 16 == 0;
+  return !p.in_bf16 && !p.out_bf16 && !p.stem && !p.x_c8 && !p.y_c8 && p.Kp % 16 == 0 && p.Cin % 16 == 0 &&
+         (!p.x2 || p.Cin2 % 16 == 0) && p.Cout % 16 == 0;
 }
 
 // N tile of conv_dma_x3: the widest 16*NT (NT = 8 or <= 6: a stage is (16 MT + 3 NT) KiB, two per
@@ -1757,9 +1756,9 @@ bool stem_bf16_supported(const ConvParams& p) {
 }
 
 bool stem_x3_supported(const ConvParams& p) {
-  return !(p.vflags & CLASFV_VARIANT_NO_STEM_X3) && p.stem && !p.out_bf16 && !p.in_bf16 && p.Cin == 4 &&
-         p.Cout == 48 && p.KT == 1 && p.KH == 7 && p.KW == 7 && p.st == 1 && p.sh == 2 && p.sw == 2 && p.pt == 0 &&
-         p.ph == 3 && p.pw == 3 && !p.res && !p.x_c8 && p.To == p.Ti && (size_t)p.M < ((size_t)1 << 31);
+  return p.stem && !p.out_bf16 && !p.in_bf16 && p.Cin == 4 && p.Cout == 48 && p.KT == 1 && p.KH == 7 && p.KW == 7 &&
+         p.st == 1 && p.sh == 2 && p.sw == 2 && p.pt == 0 && p.ph == 3 && p.pw == 3 && !p.res && !p.x_c8 &&
+         p.To == p.Ti && (size_t)p.M < ((size_t)1 << 31);
 }
 
 // p.w: hi, mid, lo images, each [48][7 kh][8 kw][4 c] bf16 (engine.hip, clasfv_finalize).

@@ -73,6 +73,19 @@ int pad_channels(int c, bool bf16) {
 
 enum Role { STEM_S, STEM_T, SP1, TP1, SP2, TP2, DS, PROJ };
 
+// The weight images of a Conv (Conv::img); a kKernels row names the one its kernel takes as ConvParams::w.
+enum Image {
+  IMG_W,       // weights [cout_alloc][Kp], dtype of the conv's input
+  IMG_WINO,    // Winograd F(2x2,3x3) transformed weights (fp32 stride-1 1x3x3 convs)
+  IMG_WINO4,   // Winograd F(4x4,3x3) transformed weights (the same convs, cout_p % 48 == 0)
+  IMG_WINO4W,  // the same for conv_wino4w's wide output-channel blocks (wino4w_ntn(cout_p) > 0)
+  IMG_WINO4R,  // the same values in conv_wino4r's (12 row waves) order
+  IMG_WINOT,   // Winograd F(4,3)-in-time transformed weights (fp32 stride-1 3x1x1 convs)
+  IMG_WS16,    // the stem's bf16 pieces: hi, lo [64][7 kh][8 kw][4 c] (bf16 engines); hi, mid, lo [48][7][8][4] (fp32)
+  IMG_X3,      // fp32 engines' implicit-GEMM convs: 3-piece bf16 image for conv_dma_x3
+  N_IMAGES
+};
+
 struct Conv {
   Role role;
   std::string w, bn;  // parameter name prefixes (".weight" / BN module)
@@ -81,28 +94,15 @@ struct Conv {
   int K, Kp, cout_alloc;
   int cin2 = 0;  // second input of a dual 1x1x1 conv (decoder P01 = W0 f_stem + W1 f_layer1)
   int stem = 0, in_bf16 = 0, out_bf16 = 0;
-  void* dw = nullptr;     // weights, dtype of the conv's input
-  float* db = nullptr;    // folded-BN bias (fp32)
-  void* dwino = nullptr;  // Winograd F(2x2,3x3) transformed weights (fp32 stride-1 1x3x3 convs)
-  void* dwino4 = nullptr;  // Winograd F(4x4,3x3) transformed weights (the same convs, cout_p % 48 == 0)
-  void* dwino4w = nullptr;  // the same for conv_wino4w's wide output-channel blocks (wino4w_ntn(cout_p) > 0)
-  void* dwino4r = nullptr;  // the same values in conv_wino4r's (12 row waves) order
-  void* dwinot = nullptr;  // Winograd F(4,3)-in-time transformed weights (fp32 stride-1 3x1x1 convs)
-  void* dws16 = nullptr;    // bf16 stem weights, hi and lo images [64][7 kh][8 kw][4 c] (bf16 engines);
-                            // fp32 engines: hi, mid and lo images [48][7][8][4] (conv_stem_x3)
-  void* dx3 = nullptr;      // fp32 engines' implicit-GEMM convs: 3-piece bf16 image for conv_dma_x3
+  void* img[N_IMAGES] = {};  // device weight images, by Image
+  float* db = nullptr;       // folded-BN bias (fp32)
 };
-
-// Every weight image of a Conv; a kKernels row names the one its kernel takes as ConvParams::w.
-using ConvImage = void* Conv::*;
-constexpr ConvImage kConvImages[] = {&Conv::dw,      &Conv::dwino,  &Conv::dwino4, &Conv::dwino4w,
-                                     &Conv::dwino4r, &Conv::dwinot, &Conv::dws16,  &Conv::dx3};
 
 // Frees every device image of c and its bias, and nulls the pointers.
 void free_conv_images(Conv& c) {
-  for (ConvImage img : kConvImages) {
-    (void)hipFree(c.*img);
-    c.*img = nullptr;
+  for (void*& p : c.img) {
+    (void)hipFree(p);
+    p = nullptr;
   }
   (void)hipFree(c.db);
   c.db = nullptr;
@@ -122,39 +122,32 @@ bool use_wino(const Conv& c, bool bf16, int vflags) {
          c.sw == 1 && c.cin_p % 16 == 0 && c.cout_p % 48 == 0;
 }
 
-// The weight images clasfv_finalize uploads for a conv (after layout_conv) beside Conv::dw, for an engine
-// of this compute dtype and these variants: the upload functions ask here, and so does mark_images, so
-// pick_kernel sees the same images on a finalized handle and on max_clips' device-less plan.
-struct Images {
-  bool x3, wino, wino4, wino4w, wino4r, winot, ws16;
-};
-Images images_of(const Conv& c, bool bf16, int vflags) {
-  Images m{};
-  m.x3 = !c.in_bf16 && !c.stem && c.Kp % 16 == 0;  // conv_dma_x3's split image of the same weights
-  m.wino = use_wino(c, bf16, vflags);
-  m.wino4 = m.wino && c.cout_p % 48 == 0 && c.cin_p % 8 == 0;
-  m.wino4w = m.wino && c.cin_p % 8 == 0 && wino4w_weight_floats(c.cin_p, c.cout_p);
-  m.wino4r = m.wino && c.cin_p % 8 == 0 && wino4r_weight_floats(c.cin_p, c.cout_p);
-  m.winot = use_winot(c, bf16, vflags);
+// The weight images clasfv_finalize uploads for a conv (after layout_conv), as a mask of 1 << Image, for an
+// engine of this compute dtype and these variants: the upload functions ask here, and so does mark_images,
+// so pick_kernel sees the same images on a finalized handle and on max_clips' device-less plan.
+constexpr int bit(Image i) { return 1 << i; }
+int images_of(const Conv& c, bool bf16, int vflags) {
+  int m = bit(IMG_W);
+  if (!c.in_bf16 && !c.stem && c.Kp % 16 == 0) m |= bit(IMG_X3);  // conv_dma_x3's split image of the same weights
+  if (use_wino(c, bf16, vflags)) {
+    m |= bit(IMG_WINO);
+    if (c.cout_p % 48 == 0 && c.cin_p % 8 == 0) m |= bit(IMG_WINO4);
+    if (c.cin_p % 8 == 0 && wino4w_weight_floats(c.cin_p, c.cout_p)) m |= bit(IMG_WINO4W);
+    if (c.cin_p % 8 == 0 && wino4r_weight_floats(c.cin_p, c.cout_p)) m |= bit(IMG_WINO4R);
+  }
+  if (use_winot(c, bf16, vflags)) m |= bit(IMG_WINOT);
   // conv_stem_x3's pieces (fp32 engines, 48 channels) / conv_stem_bf16's (bf16 engines, 64)
-  m.ws16 = c.stem && c.kh == 7 && c.kw == 7 && c.cin <= 4 && (bf16 ? c.cout_p == 64 : c.cout_p == 48);
+  if (c.stem && c.kh == 7 && c.kw == 7 && c.cin <= 4 && (bf16 ? c.cout_p == 64 : c.cout_p == 48)) m |= bit(IMG_WS16);
   return m;
 }
-// Marks the images of images_of (and Conv::dw) present without a device: pointers that are never read.
+// Marks the images of images_of present without a device: pointers that are never read.
 void mark_images(Conv& c, bool bf16, int vflags) {
-  const Images m = images_of(c, bf16, vflags);
+  const int m = images_of(c, bf16, vflags);
   void* const some = &c;
-  c.dw = some;
+  for (int i = 0; i < N_IMAGES; ++i) c.img[i] = (m >> i & 1) ? some : nullptr;
   // the folded-BN bias of a backbone conv (the projections have none): stem_bf16_supported asks for it, and
   // without it the device-less plan put the bf16 engines' stem on conv_stem_f32
   c.db = c.role != PROJ ? reinterpret_cast<float*>(some) : nullptr;
-  c.dx3 = m.x3 ? some : nullptr;
-  c.dwino = m.wino ? some : nullptr;
-  c.dwino4 = m.wino4 ? some : nullptr;
-  c.dwino4w = m.wino4w ? some : nullptr;
-  c.dwino4r = m.wino4r ? some : nullptr;
-  c.dwinot = m.winot ? some : nullptr;
-  c.dws16 = m.ws16 ? some : nullptr;
 }
 
 // Every CLASFV_VARIANT_* bit of include/clasfv.h with the environment variable that sets it: a switch
@@ -398,30 +391,35 @@ uint16_t to_bf16(float f) {
   return (uint16_t)(u >> 16);
 }
 
-int upload_bf16(const std::vector<float>& h, void** d) {
-  std::vector<uint16_t> b(h.size());
-  for (size_t i = 0; i < h.size(); ++i) b[i] = to_bf16(h[i]);
+int upload_u16(const std::vector<uint16_t>& b, void** d) {
   HIP_TRY(hipMalloc(d, b.size() * sizeof(uint16_t)));
   HIP_TRY(hipMemcpy(*d, b.data(), b.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
   return CLASFV_OK;
 }
 
-// Folded, padded [cout_alloc][Kp] weight image of one conv. `wsrc(o, c, tap)` returns the raw weight.
+int upload_bf16(const std::vector<float>& h, void** d) {
+  std::vector<uint16_t> b(h.size());
+  for (size_t i = 0; i < h.size(); ++i) b[i] = to_bf16(h[i]);
+  return upload_u16(b, d);
+}
+
+// Folded, padded [cout_alloc][Kp] weight image of one conv. `wsrc(o, c, tap)` returns the raw weight of
+// input column c < cols (c.cin; the concatenated width of a decoder projection, whose one tap has no stride).
 template <class F>
-int upload_conv(Conv& c, F wsrc, const std::vector<double>& scale, const std::vector<double>& shift, bool has_bias) {
+int upload_conv(Conv& c, int cols, F wsrc, const std::vector<double>& scale, const std::vector<double>& shift,
+                bool has_bias) {
   std::vector<float> w((size_t)c.cout_alloc * c.Kp, 0.f);
   const int taps = c.kt * c.kh * c.kw;
   for (int o = 0; o < c.cout; ++o)
     for (int tap = 0; tap < taps; ++tap)
-      for (int ci = 0; ci < c.cin; ++ci)
+      for (int ci = 0; ci < cols; ++ci)
         w[(size_t)o * c.Kp + (size_t)tap * c.cin_p + ci] = (float)((double)wsrc(o, ci, tap) * scale[o]);
-  int rc = c.in_bf16 ? upload_bf16(w, &c.dw) : upload(w, &c.dw);
+  int rc = c.in_bf16 ? upload_bf16(w, &c.img[IMG_W]) : upload(w, &c.img[IMG_W]);
   if (rc) return rc;
-  if (images_of(c, false, 0).x3) {  // conv_dma_x3's split image of the same weights
+  if (images_of(c, false, 0) & bit(IMG_X3)) {  // conv_dma_x3's split image of the same weights
     std::vector<uint16_t> x3(dma_x3_weight_elems(c.cout_alloc, c.Kp));
     dma_x3_weight_image(w.data(), c.cout_alloc, c.Kp, x3.data());
-    HIP_TRY(hipMalloc(&c.dx3, x3.size() * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(c.dx3, x3.data(), x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if ((rc = upload_u16(x3, &c.img[IMG_X3]))) return rc;
   }
   if (has_bias) {
     std::vector<float> b(c.cout_alloc, 0.f);
@@ -447,22 +445,20 @@ int upload_wino_images(Conv& c, const std::vector<float>& w, const std::vector<d
   int rc;
   std::vector<float> u((size_t)16 * c.cin_p * c.cout_p);
   wino_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u.data());
-  if ((rc = upload(u, &c.dwino))) return rc;
-  const Images m = images_of(c, false, 0);  // (called for a use_wino conv: the widths decide the rest)
-  if (m.wino4) {
-    std::vector<float> u4(wino4_weight_floats(c.cin_p, c.cout_p));
-    wino4_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u4.data());
-    if ((rc = upload(u4, &c.dwino4))) return rc;
-  }
-  if (m.wino4w) {
-    std::vector<float> uw(wino4w_weight_floats(c.cin_p, c.cout_p));
-    wino4w_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, uw.data());
-    if ((rc = upload(uw, &c.dwino4w))) return rc;
-  }
-  if (m.wino4r) {
-    std::vector<float> ur(wino4r_weight_floats(c.cin_p, c.cout_p));
-    wino4r_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, ur.data());
-    if ((rc = upload(ur, &c.dwino4r))) return rc;
+  if ((rc = upload(u, &c.img[IMG_WINO]))) return rc;
+  const int m = images_of(c, false, 0);  // (called for a use_wino conv: the widths decide the rest)
+  const struct {
+    Image img;
+    size_t (*floats)(int cin_p, int cout_p);
+    void (*transform)(const double* w, int cout, int cin, int cout_p, int cin_p, float* U);
+  } f4x4[] = {{IMG_WINO4, wino4_weight_floats, wino4_transform_weights},
+              {IMG_WINO4W, wino4w_weight_floats, wino4w_transform_weights},
+              {IMG_WINO4R, wino4r_weight_floats, wino4r_transform_weights}};
+  for (const auto& f : f4x4) {
+    if (!(m & bit(f.img))) continue;
+    std::vector<float> u4(f.floats(c.cin_p, c.cout_p));
+    f.transform(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u4.data());
+    if ((rc = upload(u4, &c.img[f.img]))) return rc;
   }
   return CLASFV_OK;
 }
@@ -472,7 +468,7 @@ int upload_winot_image(Conv& c, const std::vector<float>& w, const std::vector<d
   const std::vector<double> wf = folded_weights(c, w, s, 3);
   std::vector<float> u((size_t)6 * c.cin_p * c.cout_p);
   winot_transform_weights(wf.data(), c.cout, c.cin, c.cout_p, c.cin_p, u.data());
-  return upload(u, &c.dwinot);
+  return upload(u, &c.img[IMG_WINOT]);
 }
 
 // fn(k, raw weight, its output channel's BN scale) for every 7x7 tap of the stem, k its offset in a
@@ -486,9 +482,9 @@ void for_stem_taps(const Conv& c, const std::vector<float>& w, const std::vector
           fn((((size_t)o * 7 + kh) * 8 + kw) * 4 + ci, w[((size_t)o * c.cin + ci) * 49 + kh * 7 + kw], s[o]);
 }
 
-// The stem's split-bf16 images (Conv::dws16); each kernel's pieces keep their own rounding.
+// The stem's split-bf16 images (IMG_WS16); each kernel's pieces keep their own rounding.
 int upload_stem_images(Conv& c, const std::vector<float>& w, const std::vector<double>& s, bool bf16) {
-  if (!images_of(c, bf16, 0).ws16) return CLASFV_OK;
+  if (!(images_of(c, bf16, 0) & bit(IMG_WS16))) return CLASFV_OK;
   if (!bf16) {  // conv_stem_x3's pieces
     const size_t img = (size_t)48 * 7 * 8 * 4;
     std::vector<float> ws(3 * img, 0.f);  // hi, mid, lo: bf16 of the remainder, in double
@@ -502,7 +498,7 @@ int upload_stem_images(Conv& c, const std::vector<float>& w, const std::vector<d
         r -= f;
       }
     });
-    return upload_bf16(ws, &c.dws16);
+    return upload_bf16(ws, &c.img[IMG_WS16]);
   }
   {  // conv_stem_bf16's K order
     const size_t img = (size_t)64 * 7 * 8 * 4;
@@ -515,7 +511,7 @@ int upload_stem_images(Conv& c, const std::vector<float>& w, const std::vector<d
       ws[k] = hi;
       ws[img + k] = v - hi;
     });
-    return upload_bf16(ws, &c.dws16);
+    return upload_bf16(ws, &c.img[IMG_WS16]);
   }
   return CLASFV_OK;
 }
@@ -529,11 +525,11 @@ int finalize_conv(clasfv_engine* h, Conv& c, bool bf16) {
   const int taps = c.kt * c.kh * c.kw;
   const int cin = c.cin;
   int rc = upload_conv(
-      c, [&](int o, int ci, int tap) { return w[((size_t)o * cin + ci) * taps + tap]; }, s, t, true);
-  const Images m = images_of(c, bf16, h->tune.vflags);
-  if (!rc && m.wino) rc = upload_wino_images(c, w, s);
+      c, cin, [&](int o, int ci, int tap) { return w[((size_t)o * cin + ci) * taps + tap]; }, s, t, true);
+  const int m = images_of(c, bf16, h->tune.vflags);
+  if (!rc && (m & bit(IMG_WINO))) rc = upload_wino_images(c, w, s);
   if (!rc) rc = upload_stem_images(c, w, s, bf16);
-  if (!rc && m.winot) rc = upload_winot_image(c, w, s);
+  if (!rc && (m & bit(IMG_WINOT))) rc = upload_winot_image(c, w, s);
   return rc;
 }
 
@@ -549,13 +545,9 @@ int finalize_projections(clasfv_engine* h) {
     Conv& c = h->proj[i];
     free_conv_images(c);
     const int o0 = col0[i];
-    Conv tmp = c;  // upload_conv walks cin: give it the concatenated width
-    tmp.cin = tmp.cin_p = c.cin + c.cin2;
-    int rc = upload_conv(
-        tmp, [&](int o, int ci, int) { return w1[(size_t)o * 1024 + o0 + ci]; }, s, zero, false);
-    if (rc) return rc;
-    c.dw = tmp.dw;
-    c.dx3 = tmp.dx3;
+    if (int rc = upload_conv(
+            c, c.cin + c.cin2, [&](int o, int ci, int) { return w1[(size_t)o * 1024 + o0 + ci]; }, s, zero, false))
+      return rc;
   }
   return CLASFV_OK;
 }
@@ -600,9 +592,7 @@ int finalize_decoder(clasfv_engine* h) {
   h->w2x3 = nullptr;
   int rc = upload(b1, &h->b1);
   if (!rc) rc = upload(w2f, &h->w2);
-  if (!rc && hipMalloc(&h->w2x3, w2x3.size() * sizeof(uint16_t)) != hipSuccess) rc = fail(CLASFV_EHIP, "hipMalloc");
-  if (!rc && hipMemcpy(h->w2x3, w2x3.data(), w2x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(CLASFV_EHIP, "hipMemcpy");
+  if (!rc) rc = upload_u16(w2x3, &h->w2x3);
   if (!rc) rc = upload(b2, &h->b2);
   if (!rc) rc = upload(whf, &h->wh);
   if (!rc) rc = upload(bhf, &h->bh);
@@ -681,7 +671,7 @@ double xg_gemm(const Conv& c, const Shape5& out) {  // launch_conv's kernels: 12
   return 2.0 * (ceil(m / 128.0) * 128.0) * c.cout_p * (double)c.Kp * 1e-9;
 }
 
-// The conv kernels run_conv dispatches to. kKernels has one row per enumerator, in this order.
+// The conv kernels pick_kernel chooses among. kKernels has one row per enumerator, in this order.
 enum Kernel {
   K_WINO4R, K_WINO4W, K_WINO4, K_WINO_Q, K_WINO, K_STEM_BF16, K_STEM_X3, K_WINOT, K_PATCH_BF16, K_PATCH32_BF16,
   K_TWALK_BF16, K_PROJ_X3, K_DMA_X3, K_STEM_F32, K_DMA_W, K_DMA
@@ -690,7 +680,11 @@ enum Kernel {
 struct KernelInfo {
   Kernel id;
   const char* name;  // reported by clasfv_kernel_timing and clasfv_run_conv
-  ConvImage image;   // the Conv image the kernel takes as ConvParams::w
+  Image image;       // the Conv image the kernel takes as ConvParams::w
+  int off;           // the CLASFV_VARIANT_* bits that switch the kernel off, any of them
+  // the kernel's gate over the conv's parameters; nullptr: an implicit GEMM of last resort, which takes any
+  // conv. (A bit that chooses a form inside a launcher is read by the gate the launcher re-asks, not here.)
+  bool (*supported)(const ConvParams& p);
   // 8-channel-blocked layout: kernels that may write it (y_c8) / read it (x_c8). Measured per
   // producer (30 clips, profiles/r02j_*): stem and conv_wino_q (layer1, layer2) write the blocked
   // layout at no cost while the temporal kernels after them gain 7-24 %; conv_wino (layer3) broke
@@ -698,23 +692,28 @@ struct KernelInfo {
   bool writes_c8, reads_c8;
   double (*xgflop)(const Conv& c, const Shape5& out);  // MFMA work of one launch, see above
 };
+constexpr int V_NO4 = CLASFV_VARIANT_NO_WINO4, V_NO4W = CLASFV_VARIANT_NO_WINO4W, V_NO4R = CLASFV_VARIANT_NO_WINO4R,
+              V_NOPB = CLASFV_VARIANT_NO_PATCH_BF16;
 constexpr KernelInfo kKernels[] = {
-    {K_WINO4R, "conv_wino4r", &Conv::dwino4r, true, false, xg_wino4r},
-    {K_WINO4W, "conv_wino4w", &Conv::dwino4w, true, false, xg_wino4w},
-    {K_WINO4, "conv_wino4", &Conv::dwino4, true, false, xg_wino4},
-    {K_WINO_Q, "conv_wino_q", &Conv::dwino, true, false, xg_wino},
-    {K_WINO, "conv_wino", &Conv::dwino, false, false, xg_wino},
-    {K_STEM_BF16, "conv_stem_bf16", &Conv::dws16, false, false, xg_stem_bf16},
-    {K_STEM_X3, "conv_stem_x3", &Conv::dws16, true, false, xg_stem_x3},
-    {K_WINOT, "conv_winot", &Conv::dwinot, false, true, xg_winot},
-    {K_PATCH_BF16, "conv_patch_bf16", &Conv::dw, false, false, xg_patch_bf16},
-    {K_PATCH32_BF16, "conv_patch32_bf16", &Conv::dw, false, false, xg_patch32_bf16},
-    {K_TWALK_BF16, "conv_twalk_bf16", &Conv::dw, false, false, xg_twalk_bf16},
-    {K_PROJ_X3, "conv_proj_x3", &Conv::dx3, false, false, xg_proj_x3},
-    {K_DMA_X3, "conv_dma_x3", &Conv::dx3, false, false, xg_dma_x3},
-    {K_STEM_F32, "conv_stem_f32", &Conv::dw, true, false, xg_gemm},
-    {K_DMA_W, "conv_dma_w", &Conv::dw, false, false, xg_gemm},
-    {K_DMA, "conv_dma", &Conv::dw, false, false, xg_gemm},
+    {K_WINO4R, "conv_wino4r", IMG_WINO4R, V_NO4 | V_NO4W | V_NO4R, wino4r_supported, true, false, xg_wino4r},
+    {K_WINO4W, "conv_wino4w", IMG_WINO4W, V_NO4 | V_NO4W, wino4w_supported, true, false, xg_wino4w},
+    {K_WINO4, "conv_wino4", IMG_WINO4, V_NO4, wino4_supported, true, false, xg_wino4},
+    {K_WINO_Q, "conv_wino_q", IMG_WINO, CLASFV_VARIANT_NO_WINO_PATCH, winoq_supported, true, false, xg_wino},
+    {K_WINO, "conv_wino", IMG_WINO, 0, wino_supported, false, false, xg_wino},
+    {K_STEM_BF16, "conv_stem_bf16", IMG_WS16, CLASFV_VARIANT_NO_STEM_BF16, stem_bf16_supported, false, false, xg_stem_bf16},
+    {K_STEM_X3, "conv_stem_x3", IMG_WS16, CLASFV_VARIANT_NO_STEM_X3, stem_x3_supported, true, false, xg_stem_x3},
+    {K_WINOT, "conv_winot", IMG_WINOT, 0, winot_supported, false, true, xg_winot},
+    {K_PATCH_BF16, "conv_patch_bf16", IMG_W, V_NOPB, patch_bf16_supported, false, false, xg_patch_bf16},
+    {K_PATCH32_BF16, "conv_patch32_bf16", IMG_W, V_NOPB | CLASFV_VARIANT_NO_PATCH32, patch32_bf16_supported, false, false,
+     xg_patch32_bf16},
+    {K_TWALK_BF16, "conv_twalk_bf16", IMG_W, V_NOPB | CLASFV_VARIANT_NO_TWALK, twalk_bf16_supported, false, false,
+     xg_twalk_bf16},
+    {K_PROJ_X3, "conv_proj_x3", IMG_X3, CLASFV_VARIANT_NO_PROJ_X3 | CLASFV_VARIANT_NO_DMA_X3, proj_x3_supported, false, false,
+     xg_proj_x3},
+    {K_DMA_X3, "conv_dma_x3", IMG_X3, CLASFV_VARIANT_NO_DMA_X3, dma_x3_supported, false, false, xg_dma_x3},
+    {K_STEM_F32, "conv_stem_f32", IMG_W, 0, nullptr, true, false, xg_gemm},
+    {K_DMA_W, "conv_dma_w", IMG_W, 0, dma_w_ok, false, false, xg_gemm},
+    {K_DMA, "conv_dma", IMG_W, 0, nullptr, false, false, xg_gemm},
 };
 constexpr bool kernels_in_order() {
   int i = 0;
@@ -732,7 +731,7 @@ ConvParams conv_params(const Conv& c, const Shape5& in, Shape5& out) {
   out.w = (in.w + 2 * c.pw - c.kw) / c.sw + 1;
   out.c = c.cout_p;
   ConvParams p{};
-  p.w = c.dw;
+  p.w = c.img[IMG_W];
   p.bias = c.db;
   p.N = in.n, p.Ti = in.t, p.Hi = in.h, p.Wi = in.w, p.Cin = in.c;
   p.To = out.t, p.Ho = out.h, p.Wo = out.w, p.Cout = out.c;
@@ -747,38 +746,30 @@ ConvParams conv_params(const Conv& c, const Shape5& in, Shape5& out) {
   return p;
 }
 
-// The kernel run_conv launches for c with parameters p (p.vflags selects A/B variants).
-Kernel pick_kernel(const Conv& c, ConvParams p) {
+// Whether kernel k can run c with parameters p: its weight image is there, no variant bit of p.vflags
+// switches it off, and its gate accepts p.
+bool can_run(Kernel k, const Conv& c, const ConvParams& p) {
+  const KernelInfo& ki = kKernels[k];
+  return c.img[ki.image] && !(p.vflags & ki.off) && (!ki.supported || ki.supported(p));
+}
+
+// The kernel of c with parameters p (p.vflags selects A/B variants): the first of this list that can run it.
+Kernel pick_kernel(const Conv& c, const ConvParams& p) {
   // 7x7 maps (layer4 at 112x112 clips): the split-bf16 direct GEMM beats F(4x4)'s partial edge tiles
   // (convbench 0.284 vs 0.312 ms per 1152-channel launch, profiles/r03p_dma_x3_tiles.txt); per-clip
   // shape rule
-  if (c.dwino4 && c.dx3 && p.Ho * p.Wo <= 64 && !p.y_c8 && dma_x3_supported(p)) return K_DMA_X3;
-  const int no4 = p.vflags & (CLASFV_VARIANT_NO_WINO4 | CLASFV_VARIANT_NO_WINO4W);
-  if (c.dwino4r && !no4 && !(p.vflags & CLASFV_VARIANT_NO_WINO4R) && wino4r_supported(p)) return K_WINO4R;
-  if (c.dwino4w && !no4 && wino4w_supported(p)) return K_WINO4W;
-  if (c.dwino4 && !(p.vflags & CLASFV_VARIANT_NO_WINO4) && wino4_supported(p)) return K_WINO4;
-  if (c.dwino) {
-    const bool no_patch = (p.vflags & CLASFV_VARIANT_NO_WINO_PATCH) != 0;
-    if (!no_patch && winoq_supported(p)) return K_WINO_Q;
-    if (wino_supported(p)) return K_WINO;
-  }
-  if (c.dws16 && !(p.vflags & CLASFV_VARIANT_NO_STEM_BF16) && stem_bf16_supported(p)) return K_STEM_BF16;
-  if (c.dws16 && stem_x3_supported(p)) return K_STEM_X3;
+  if (c.img[IMG_WINO4] && p.Ho * p.Wo <= 64 && !p.y_c8 && can_run(K_DMA_X3, c, p)) return K_DMA_X3;
+  for (Kernel k : {K_WINO4R, K_WINO4W, K_WINO4, K_WINO_Q, K_WINO, K_STEM_BF16, K_STEM_X3})
+    if (can_run(k, c, p)) return k;
   // temporal convs on <= 256-voxel clip maps (layer4, T = 4): split-K 4 on the split-bf16 direct GEMM
   // beats the one-tile-row F(4,3) form (convbench 0.119 vs 0.145 ms with both split sums)
-  if (c.dwinot && c.dx3 && (long)p.To * p.Ho * p.Wo <= 256 && !p.x_c8 && !p.y_c8 && dma_x3_supported(p))
+  if (c.img[IMG_WINOT] && (long)p.To * p.Ho * p.Wo <= 256 && !p.x_c8 && !p.y_c8 && can_run(K_DMA_X3, c, p))
     return K_DMA_X3;
-  if (c.dwinot && winot_supported(p)) return K_WINOT;
-  if (c.dx3 && !(p.vflags & CLASFV_VARIANT_NO_PROJ_X3) && proj_x3_supported(p)) return K_PROJ_X3;
-  if (!(p.vflags & (CLASFV_VARIANT_NO_PATCH_BF16 | CLASFV_VARIANT_NO_PATCH32)) && patch32_bf16_supported(p))
-    return K_PATCH32_BF16;
-  if (!(p.vflags & (CLASFV_VARIANT_NO_PATCH_BF16 | CLASFV_VARIANT_NO_TWALK)) && twalk_bf16_supported(p))
-    return K_TWALK_BF16;
-  if (!(p.vflags & CLASFV_VARIANT_NO_PATCH_BF16) && patch_bf16_supported(p)) return K_PATCH_BF16;
-  if (c.dx3 && dma_x3_supported(p)) return K_DMA_X3;
+  for (Kernel k : {K_WINOT, K_PROJ_X3, K_PATCH32_BF16, K_TWALK_BF16, K_PATCH_BF16, K_DMA_X3})
+    if (can_run(k, c, p)) return k;
   if (c.stem) return K_STEM_F32;
   // bf16 direct convs with whole 128-B tap rows (launch_dma takes conv_dma_w at the 128-row M tile)
-  return dma_w_ok(p) ? K_DMA_W : K_DMA;
+  return can_run(K_DMA_W, c, p) ? K_DMA_W : K_DMA;
 }
 
 // Whether the mid tensor between producer `a` (input shape `in`) and consumer `b` goes through HBM
@@ -843,69 +834,82 @@ const char* gemm_size_error(const KernelInfo& k, const ConvParams& p, const Shap
   return nullptr;
 }
 
-// What run_conv decided, for a caller that records it (clasfv_forward_plan): the parameters the launcher
-// takes and the split-K factor the per-clip rule asked for (p.n_split is the one granted).
-struct ConvBuilt {
-  ConvParams p;
-  int split_asked;
+// One conv call: the conv, its tensors and layouts, and the scratch offered for split-K sums (none: no split).
+struct ConvCall {
+  const Conv* conv;
+  Shape5 in;                 // of x (and x2)
+  const void *x, *x2, *res;  // x2: the dual projection's second input; res: the residual added to y; or nullptr
+  void* y;
+  bool relu;
+  int x_c8, y_c8;
+  void* scratch;
+  size_t scratch_bytes;
 };
 
-// Runs c on the kernel pick_kernel chooses; *kernel is its kKernels row once chosen. A shape that kernel
-// cannot address is refused (CLASFV_EBADSHAPE) before anything is launched; dry: stop after that check.
-// *built, when given, is what the launcher is (or, dry, would be) called with.
-int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-             hipStream_t s, const void* zero_block, const void* x2, const KernelInfo** kernel, const Tuning& tu,
-             int x_c8 = 0, int y_c8 = 0, void* scratch = nullptr, size_t scratch_bytes = 0, bool dry = false,
-             ConvBuilt* built = nullptr) {
+// What decide_conv decided about a call: all launch_built needs, and all clasfv_forward_plan records.
+struct ConvBuilt {
+  const Conv* conv;
+  const KernelInfo* kernel;  // the kKernels row, from the moment it is chosen: also of a call refused after that
+  ConvParams p;              // what the launcher takes
+  Shape5 out;
+  int split_asked;  // the split-K factor the per-clip rule asked for (p.n_split is the one granted)
+  int mt, bn;       // the implicit GEMMs' tile
+};
+
+// Decides how call cc runs on an engine with tuning tu and padding source zero_block: b is the kernel pick_kernel
+// chooses and its launch. A shape that kernel cannot address is refused (CLASFV_EBADSHAPE). Launches nothing.
+int decide_conv(const ConvCall& cc, const void* zero_block, const Tuning& tu, ConvBuilt& b) {
+  const Conv& c = *cc.conv;
+  const Shape5& in = cc.in;
+  b = ConvBuilt{&c};
   if (in.c != c.cin_p) return fail(CLASFV_EINVAL, "internal: channel mismatch");
-  ConvParams p = conv_params(c, in, out);
-  p.vflags = tu.vflags;
-  p.patch_nt = tu.patch_nt;
-  p.x = x;
-  p.res = res;
-  p.y = y;
-  p.relu = relu ? 1 : 0;
-  p.zero = zero_block;
-  p.x2 = x2;
-  p.x_c8 = x_c8;
-  p.y_c8 = y_c8;
+  Shape5& out = b.out;
+  ConvParams& p = b.p = conv_params(c, in, out);
+  p.vflags = tu.vflags, p.patch_nt = tu.patch_nt;
+  p.x = cc.x, p.x2 = cc.x2, p.res = cc.res, p.y = cc.y, p.zero = zero_block;
+  p.relu = cc.relu ? 1 : 0, p.x_c8 = cc.x_c8, p.y_c8 = cc.y_c8;
   // the kernel of one clip of the shape, whatever the batch (conv_size_error)
   ConvParams p1 = p;
-  p1.N = 1;
-  p1.M = (int)(out.voxels() / out.n);
-  const KernelInfo& k1 = kKernels[pick_kernel(c, p1)];
+  p1.N = 1, p1.M = (int)(out.voxels() / out.n);
+  const KernelInfo& k = kKernels[pick_kernel(c, p1)];
   const Kernel kn = pick_kernel(c, p);
-  *kernel = &k1;
-  if (const char* why = conv_size_error(k1.id, kn, in, out))
-    return fail(CLASFV_EBADSHAPE, std::string(k1.name) + ": " + why + " (N=" + std::to_string(in.n) + " T=" +
+  b.kernel = &k;
+  if (const char* why = conv_size_error(k.id, kn, in, out))
+    return fail(CLASFV_EBADSHAPE, std::string(k.name) + ": " + why + " (N=" + std::to_string(in.n) + " T=" +
                                       std::to_string(in.t) + " H=" + std::to_string(in.h) + " W=" + std::to_string(in.w) +
                                       " C=" + std::to_string(in.c) + ")");
-  const KernelInfo& k = k1;
-  if ((y_c8 && !k.writes_c8) || (x_c8 && !k.reads_c8))
+  if ((p.y_c8 && !k.writes_c8) || (p.x_c8 && !k.reads_c8))
     return fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
-  if (x_c8 && k.id == K_WINOT && !winot_c8_ok(p))  // only launch_winot's conv_winot5 form reads the layout
+  if (p.x_c8 && k.id == K_WINOT && !winot_c8_ok(p))  // only launch_winot's conv_winot5 form reads the layout
     return winot_c8_ok(p1) ? fail(CLASFV_EBADSHAPE, "conv_winot: the 8-channel-blocked input has 2^32 bytes or more")
                            : fail(CLASFV_EINVAL, "internal: 8-channel-blocked layout on an unsupported kernel");
-  p.w = c.*k.image;
-  int mt = 2, bn = 0;  // the implicit GEMMs' tile
-  int asked = 1;       // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
+  p.w = c.img[k.image];
+  b.mt = 2, b.bn = 0;
+  int asked = 1;  // split-K on the smallest maps (per-clip shape rule), partial sums in the caller's scratch
   if (k.id == K_WINOT) {
     asked = winot_split_for(p);
   } else if (k.id == K_DMA_X3) {
     asked = dma_split_for(p, 2);
   } else if (k.id == K_DMA_W || k.id == K_DMA) {
-    conv_pick_tile(p.M, c.cout_p, tu.conv_nt, &mt, &bn);
-    asked = dma_split_for(p, mt);
+    conv_pick_tile(p.M, c.cout_p, tu.conv_nt, &b.mt, &b.bn);
+    asked = dma_split_for(p, b.mt);
   }
   // A caller that offers no scratch asks for no split (clasfv_run_conv's contract, and the walk's for every
   // conv that does not read MID); one that offers it is owed the rule's factor, and a scratch too small
   // for the sums shows as split_asked > n_split in the plan (tests/plan_audit.py, check E).
-  if (!scratch) asked = 1;
-  split_k(p, asked, scratch, scratch_bytes);
+  if (!cc.scratch) asked = 1;
+  split_k(p, asked, cc.scratch, cc.scratch_bytes);
+  b.split_asked = asked > 1 ? asked : 1;
   if (const char* why = gemm_size_error(k, p, in, out)) return fail(CLASFV_EBADSHAPE, std::string(k.name) + ": " + why);
-  if (built) *built = ConvBuilt{p, asked > 1 ? asked : 1};
-  if (dry) return CLASFV_OK;
-  switch (k.id) {  // no default: a Kernel without a launch is a compiler warning
+  return CLASFV_OK;
+}
+
+// Launches what decide_conv decided on stream s.
+int launch_built(const ConvBuilt& b, hipStream_t s) {
+  const Conv& c = *b.conv;
+  const ConvParams& p = b.p;
+  const int mt = b.mt, bn = b.bn;
+  switch (b.kernel->id) {  // no default: a Kernel without a launch is a compiler warning
     case K_WINO4R: HIP_TRY(launch_wino4r(p, s)); break;
     case K_WINO4W: HIP_TRY(launch_wino4w(p, s)); break;
     case K_WINO4: HIP_TRY(launch_wino4(p, s)); break;
@@ -919,9 +923,7 @@ int run_conv(const Conv& c, const void* x, const Shape5& in, void* y, Shape5& ou
     case K_TWALK_BF16: HIP_TRY(launch_twalk_bf16(p, s)); break;
     case K_PROJ_X3: HIP_TRY(launch_proj_x3(p, s)); break;
     case K_DMA_X3: HIP_TRY(launch_dma_x3(p, dma_x3_bn(c.cout_p), s)); break;
-    case K_STEM_F32:  // one N tile (48 fp32 / 64 bf16 channels)
-      HIP_TRY(launch_conv(p, 2, c.cout_p, s));
-      break;
+    case K_STEM_F32: HIP_TRY(launch_conv(p, 2, c.cout_p, s)); break;  // one N tile (48 fp32 / 64 bf16 channels)
     case K_DMA_W:
     case K_DMA: HIP_TRY(launch_conv(p, mt, bn, s)); break;
   }
@@ -1034,13 +1036,18 @@ struct DeviceGuard {
   if (_guard.err != hipSuccess)                                                                 \
     return fail(CLASFV_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(_guard.err))
 
+// The forward context of launch stream s, or nullptr when the stream has none yet.
+clasfv_engine::Ctx* find_ctx(const clasfv_engine* h, hipStream_t s) {
+  for (auto* c : h->ctxs)
+    if (c->stream == s) return c;
+  return nullptr;
+}
+
 // The forward context of launch stream s with an arena of at least `bytes`: created on first use; past
 // kMaxCtx streams the least recently used one is taken over once the device is idle (no queued work
 // can still be using its arena).
 int acquire_ctx(clasfv_engine* h, hipStream_t s, size_t bytes, clasfv_engine::Ctx** out) {
-  clasfv_engine::Ctx* cx = nullptr;
-  for (auto* c : h->ctxs)
-    if (c->stream == s) cx = c;
+  clasfv_engine::Ctx* cx = find_ctx(h, s);
   if (!cx) {
     constexpr size_t kMaxCtx = 4;
     if (h->ctxs.size() < kMaxCtx) {
@@ -1131,30 +1138,41 @@ void log_end(clasfv_engine* h, int conv) {
   }
 }
 
+// decide_conv and, unless it refuses the call, launch_built on s with the launch log around it.
+int run_conv(clasfv_engine* h, const ConvCall& cc, hipStream_t s, ConvBuilt& b) {
+  if (int rc = decide_conv(cc, h->zero, h->tune, b)) return rc;
+  log_begin(h);
+  const int rc = launch_built(b, s);
+  log_end(h, conv_index(h, *cc.conv));
+  return rc;
+}
+
 // The network's launches over n clips of (T, H, W), in forward order, on a workspace laid out by L at
-// `arena`: pack(xin) packs the input, run(...) and run_side(...) run one conv (the latter a decoder
-// projection that may overlap layer4 until join()), decode(taps, shapes, idx) runs the decoder. Each
-// returns a CLASFV code, and the first failure ends the walk. clasfv_forward launches through it;
-// max_clips walks it with runners that only ask whether every launch is inside its kernel's limits.
+// `arena`: pack(xin) packs the input, run(call, out) and run_side(call, out) run one ConvCall and give its
+// output shape (the latter a decoder projection that may overlap layer4 until join()), decode(taps, shapes,
+// idx) runs the decoder. Each returns a CLASFV code, and the first failure ends the walk. clasfv_forward
+// launches through it; the plan walks it with runners that decide every launch and launch none.
 template <class Pack, class Run, class RunSide, class Join, class Decode>
 int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, int T, int H, int W, Pack pack, Run run_,
-                 RunSide run_side, Join join, Decode decode) {
+                 RunSide run_side_, Join join, Decode decode) {
   auto buf = [&](int b) { return reinterpret_cast<void*>(arena + L.off[b]); };
   // scratch for a temporal conv reading MID: the rest of MID past its input
   const size_t mid_bytes = L.off[MID + 1] - L.off[MID];
   auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-                 const void* x2 = nullptr, int x_c8 = 0, int y_c8 = 0) {
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
+                 int x_c8, int y_c8) {
+    ConvCall cc{&c, in, xin, nullptr, res, y, relu, x_c8, y_c8, nullptr, 0};
     // Which convs may split is a property of the walk, not of sizes: those that read MID (the temporal
     // convs) are offered what is left of it, even when that is nothing, and no other conv is offered any.
     if (xin == buf(MID)) {
       const size_t used =
           std::min(mid_bytes, ((size_t)in.n * in.t * in.h * in.w * in.c * sizeof(float) + 255) / 256 * 256);
-      scratch = arena + L.off[MID] + used;
-      scratch_bytes = mid_bytes - used;
+      cc.scratch = arena + L.off[MID] + used;
+      cc.scratch_bytes = mid_bytes - used;
     }
-    return run_(c, xin, in, y, out, res, relu, x2, x_c8, y_c8, scratch, scratch_bytes);
+    return run_(cc, out);
+  };
+  auto run_side = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* x2) {
+    return run_side_(ConvCall{&c, in, xin, x2, nullptr, y, false, 0, 0, nullptr, 0}, out);
   };
   int rc;
   if ((rc = pack(buf(XIN)))) return rc;
@@ -1163,8 +1181,8 @@ int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, in
   size_t ci = 0;
   // Conv2Plus1D mid tensors (and the stem's) are 8-channel-blocked where c8_pair allows
   const int c8s = c8_pair(h->convs[0], h->convs[1], sx, h->tune);
-  if ((rc = run(h->convs[ci++], buf(XIN), sx, buf(S0), s0, nullptr, true, nullptr, 0, c8s))) return rc;
-  if ((rc = run(h->convs[ci++], buf(S0), s0, buf(X0), sx0, nullptr, true, nullptr, c8s, 0))) return rc;
+  if ((rc = run(h->convs[ci++], buf(XIN), sx, buf(S0), s0, nullptr, true, 0, c8s))) return rc;
+  if ((rc = run(h->convs[ci++], buf(S0), s0, buf(X0), sx0, nullptr, true, c8s, 0))) return rc;
   const int outs[4][2] = {{L1A, L1}, {L2A, L2}, {L3A, L3}, {L4A, L4}};
   void* cur = buf(X0);
   Shape5 cs = sx0, taps_shape[5];
@@ -1180,17 +1198,17 @@ int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, in
       const Conv* ds = (ci < h->convs.size() && h->convs[ci].role == DS) ? &h->convs[ci++] : nullptr;
       Shape5 sm, sa, sm2, so, sd;
       const int c8a = c8_pair(sp1, tp1, cs, h->tune);
-      if ((rc = run(sp1, cur, cs, buf(MID), sm, nullptr, true, nullptr, 0, c8a))) return rc;
-      if ((rc = run(tp1, buf(MID), sm, buf(TA), sa, nullptr, true, nullptr, c8a, 0))) return rc;
+      if ((rc = run(sp1, cur, cs, buf(MID), sm, nullptr, true, 0, c8a))) return rc;
+      if ((rc = run(tp1, buf(MID), sm, buf(TA), sa, nullptr, true, c8a, 0))) return rc;
       const int c8b = c8_pair(sp2, tp2, sa, h->tune);
-      if ((rc = run(sp2, buf(TA), sa, buf(MID), sm2, nullptr, true, nullptr, 0, c8b))) return rc;
+      if ((rc = run(sp2, buf(TA), sa, buf(MID), sm2, nullptr, true, 0, c8b))) return rc;
       const void* res = cur;
       if (ds) {
-        if ((rc = run(*ds, cur, cs, buf(DSB), sd, nullptr, false))) return rc;
+        if ((rc = run(*ds, cur, cs, buf(DSB), sd, nullptr, false, 0, 0))) return rc;
         res = buf(DSB);
       }
       void* out = buf(outs[li][b]);
-      if ((rc = run(tp2, buf(MID), sm2, out, so, res, true, nullptr, c8b, 0))) return rc;
+      if ((rc = run(tp2, buf(MID), sm2, out, so, res, true, c8b, 0))) return rc;
       cur = out;
       cs = so;
     }
@@ -1206,7 +1224,7 @@ int walk_network(const clasfv_engine* h, const Layout& L, char* arena, int N, in
       if ((rc = run_side(h->proj[3], taps[3], taps_shape[3], buf(PP3), sp3, nullptr))) return rc;
     }
   }
-  if ((rc = run(h->proj[4], taps[4], taps_shape[4], buf(PP4), sp4, nullptr, false))) return rc;
+  if ((rc = run(h->proj[4], taps[4], taps_shape[4], buf(PP4), sp4, nullptr, false, 0, 0))) return rc;
   if ((rc = join())) return rc;  // the side stream's projections are complete before the decoder
 
   const Shape5 tsh[4] = {sp, sp2, sp3, sp4};
@@ -1242,30 +1260,119 @@ CallerOffsets caller_offsets(int n0, int T, int H, int W) {
   return {(size_t)n0 * 3 * clip, (size_t)n0 * 2 * clip, (size_t)n0 * 4 * clip};
 }
 
+// ---- the launch plan (clasfv_forward_plan, max_clips) ---------------------------------------------------
+// clasfv_forward's sub-batch loop and walk with runners that record instead of launching: decide_conv hands
+// back the ConvParams the launcher would take, and every range below is what those parameters (or the
+// decoder's) make the kernel address. No memory is behind the addresses (only pointer identity and
+// null-ness are read). The first launch outside its kernel's limits ends the walk (CLASFV_EBADSHAPE).
+struct PlanRecorder {
+  std::vector<clasfv_plan_launch_t> launches;
+  std::vector<clasfv_plan_buffer_t> buffers;
+};
+
+// Sub-batch `sub` of a call: clips [n0, n0 + n) on the layout L of a forward of n clips.
+int plan_sub_batch(const clasfv_engine* h, PlanRecorder& rec, int sub, int n0, int n, int T, int H, int W,
+                   const Layout& L) {
+  char* const arena = reinterpret_cast<char*>(256);
+  bool side_pending = false;  // SideJoin::pending of clasfv_forward
+  for (int b = 0; b < NBUF; ++b)
+    rec.buffers.push_back({sub, n, b, 0, kBufNames[b], (int64_t)L.off[b], (int64_t)L.bytes[b], (int64_t)L.total});
+  auto launch = [&](int stream, int kind, int conv, const char* kernel) -> clasfv_plan_launch_t& {
+    clasfv_plan_launch_t l{};
+    l.sub_batch = sub, l.stream = stream, l.kind = kind, l.conv = conv, l.kernel = kernel;
+    l.split_asked = l.split_granted = 1;
+    l.x_elem = l.y_elem = 4;
+    rec.launches.push_back(l);
+    return rec.launches.back();
+  };
+  auto add = [&](clasfv_plan_launch_t& l, int buffer, int role, int write, int64_t offset, int64_t bytes) {
+    if (l.n_ranges < CLASFV_PLAN_MAX_RANGES) l.range[l.n_ranges++] = {buffer, role, write, 0, offset, bytes};
+  };
+  // a range of the arena: the buffer is the one its first byte lies in
+  auto add_arena = [&](clasfv_plan_launch_t& l, const void* p, int role, int write, int64_t bytes) {
+    const int64_t off = reinterpret_cast<const char*>(p) - arena;
+    int b = 0;
+    while (b + 1 < NBUF && off >= (int64_t)L.off[b + 1]) ++b;
+    add(l, b, role, write, off, bytes);
+  };
+  const CallerOffsets at = caller_offsets(n0, T, H, W);
+  const int64_t clip = (int64_t)T * H * W;
+  auto pack = [&](void* xin) {
+    clasfv_plan_launch_t& l = launch(0, CLASFV_PLAN_PACK, -1, "pack_input_kernel");
+    add(l, CLASFV_PLAN_EXT_CLIP, CLASFV_PLAN_X, 0, (int64_t)at.x * 4, (int64_t)n * 3 * clip * 4);
+    add_arena(l, xin, CLASFV_PLAN_Y, 1, (int64_t)n * clip * 4 * 4);  // launch_pack_input: 3 + 1 fp32 channels
+    return (int)CLASFV_OK;
+  };
+  auto conv = [&](int stream, const ConvCall& cc, Shape5& out) {
+    ConvBuilt cb;
+    if (int rc = decide_conv(cc, arena, h->tune, cb)) return rc;
+    out = cb.out;
+    const ConvParams& p = cb.p;
+    const int xe = p.in_bf16 ? 2 : 4, ye = p.out_bf16 ? 2 : 4;
+    const int64_t vin = (int64_t)p.N * p.Ti * p.Hi * p.Wi, m = (int64_t)p.N * p.To * p.Ho * p.Wo;
+    const int64_t part = (int64_t)p.n_split * m * p.Cout * 4;
+    const bool split = p.n_split > 1;
+    const int index = conv_index(h, *cc.conv);
+    clasfv_plan_launch_t& l = launch(stream, CLASFV_PLAN_CONV, index, cb.kernel->name);
+    auto describe = [&](clasfv_plan_launch_t& d) {
+      d.split_asked = cb.split_asked, d.split_granted = split ? p.n_split : 1;
+      d.x_c8 = p.x_c8, d.y_c8 = p.y_c8, d.relu = p.relu, d.has_res = p.res != nullptr;
+      d.x_elem = xe, d.y_elem = ye;
+    };
+    auto epilogue = [&](clasfv_plan_launch_t& d) {  // what the launch that writes y addresses beside its sums
+      if (p.res) add_arena(d, p.res, CLASFV_PLAN_RES, 0, m * p.Cout * ye);
+      add_arena(d, p.y, CLASFV_PLAN_Y, 1, m * p.Cout * ye);
+    };
+    describe(l);
+    add_arena(l, p.x, CLASFV_PLAN_X, 0, vin * p.Cin * xe);
+    if (p.x2) add_arena(l, p.x2, CLASFV_PLAN_X2, 0, vin * p.Cin2 * xe);
+    if (!split) {
+      epilogue(l);
+      return (int)CLASFV_OK;
+    }
+    add_arena(l, p.part, CLASFV_PLAN_PART, 1, part);
+    clasfv_plan_launch_t& ssum = launch(stream, CLASFV_PLAN_SPLIT_SUM, index, "split_sum_kernel");
+    describe(ssum);
+    add_arena(ssum, p.part, CLASFV_PLAN_PART, 0, part);
+    epilogue(ssum);
+    return (int)CLASFV_OK;
+  };
+  auto run = [&](const ConvCall& cc, Shape5& out) { return conv(0, cc, out); };
+  auto run_side = [&](const ConvCall& cc, Shape5& out) {
+    launch(1, CLASFV_PLAN_FORK, -1, "");  // ev_fork recorded on s, awaited by the side stream
+    side_pending = true;
+    return conv(1, cc, out);
+  };
+  auto join = [&]() {
+    if (side_pending) launch(0, CLASFV_PLAN_JOIN, -1, "");  // ev_join recorded on the side stream, awaited by s
+    side_pending = false;
+    return (int)CLASFV_OK;
+  };
+  auto decode = [&](const float* const tp[4], const Shape5 tsh[4], void* idx) {
+    const DecParams d = decoder_params(h, tp, tsh, nullptr, nullptr, n, T, H, W, idx);
+    if (!decoder_addressable(d)) return fail(CLASFV_EBADSHAPE, "decoder_kernel: a tap has 2^31 floats or more");
+    const int64_t table = (int64_t)decoder_index_bytes(d.T, d.H, d.W);
+    clasfv_plan_launch_t& li = launch(0, CLASFV_PLAN_DEC_INDEX, -1, "decoder_index_kernel");
+    add_arena(li, d.idx, CLASFV_PLAN_IDX, 1, table);
+    clasfv_plan_launch_t& l = launch(0, CLASFV_PLAN_DECODER, -1, "decoder_kernel");
+    for (int i = 0; i < 4; ++i)
+      add_arena(l, d.tap[i].p, CLASFV_PLAN_TAP, 0, (int64_t)d.N * d.tap[i].T * d.tap[i].H * d.tap[i].W * 64 * 4);
+    add_arena(l, d.idx, CLASFV_PLAN_IDX, 0, table);
+    add(l, CLASFV_PLAN_EXT_SEG, CLASFV_PLAN_Y, 1, (int64_t)at.seg * 4, (int64_t)d.N * 2 * clip * 4);
+    add(l, CLASFV_PLAN_EXT_MOTION, CLASFV_PLAN_Y, 1, (int64_t)at.mot * 4, (int64_t)d.N * 4 * clip * 4);
+    return (int)CLASFV_OK;
+  };
+  return walk_network(h, L, arena, n, T, H, W, pack, run, run_side, join, decode);
+}
+
 // Whether every launch of a forward over N clips of (T, H, W) is inside its kernel's limits (a CLASFV
-// code; the refusal's reason in clasfv_last_error): the forward's own walk, with nothing launched and
-// no memory behind the addresses (only pointer identity and null-ness are read).
+// code; the refusal's reason in clasfv_last_error): its plan as one pass, kept by nobody.
 int forward_fits(const clasfv_engine* h, int N, int T, int H, int W) {
   if ((int64_t)N * T * H * W >= ((int64_t)1 << 31)) return fail(CLASFV_EBADSHAPE, "the clips have 2^31 voxels or more");
   Layout L;
   make_layout(N, T, H, W, L);
-  char* const nowhere = reinterpret_cast<char*>(256);
-  auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-                 const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
-    const KernelInfo* k = nullptr;
-    return run_conv(c, xin, in, y, out, res, relu, nullptr, nowhere, x2, &k, h->tune, x_c8, y_c8, scratch, scratch_bytes,
-                    true);
-  };
-  auto run_side = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* x2) {
-    return run(c, xin, in, y, out, nullptr, false, x2, 0, 0, nullptr, 0);
-  };
-  auto ok = [](auto...) { return (int)CLASFV_OK; };
-  auto decode = [&](const float* const tp[4], const Shape5 tsh[4], void* idx) {
-    return decoder_addressable(decoder_params(h, tp, tsh, nullptr, nullptr, N, T, H, W, idx))
-               ? (int)CLASFV_OK
-               : fail(CLASFV_EBADSHAPE, "decoder_kernel: a tap has 2^31 floats or more");
-  };
-  return walk_network(h, L, nowhere, N, T, H, W, ok, run, run_side, ok, decode);
+  PlanRecorder unread;
+  return plan_sub_batch(h, unread, 0, 0, N, T, H, W, L);
 }
 
 // The largest N for which forward_fits (0: not even one clip; the reason stays in clasfv_last_error).
@@ -1280,114 +1387,11 @@ int max_clips(const clasfv_engine* h, int T, int H, int W) {
   return (int)lo;
 }
 
-// ---- the launch plan (clasfv_forward_plan) ------------------------------------------------------------
-// clasfv_forward's sub-batch loop and walk with runners that record instead of launching: run_conv in
-// its dry mode hands back the ConvParams its launcher would take, and every range below is what those
-// parameters (or the decoder's) make the kernel address. No memory is behind the addresses.
-struct PlanRecorder {
-  std::vector<clasfv_plan_launch_t> launches;
-  std::vector<clasfv_plan_buffer_t> buffers;
-};
-
 int forward_plan(const clasfv_engine* h, int N, int T, int H, int W, PlanRecorder& rec) {
   const int nb = std::min(N, max_clips(h, T, H, W));
   if (nb < 1) return forward_fits(h, 1, T, H, W);
-  char* const arena = reinterpret_cast<char*>(256);
-  bool side_pending = false;  // SideJoin::pending of clasfv_forward
   return for_sub_batches(N, nb, T, H, W, [&](int sub, int n0, int n, const Layout& L) {
-    for (int b = 0; b < NBUF; ++b)
-      rec.buffers.push_back({sub, n, b, 0, kBufNames[b], (int64_t)L.off[b], (int64_t)L.bytes[b], (int64_t)L.total});
-    auto launch = [&](int stream, int kind, int conv, const char* kernel) -> clasfv_plan_launch_t& {
-      clasfv_plan_launch_t l{};
-      l.sub_batch = sub, l.stream = stream, l.kind = kind, l.conv = conv, l.kernel = kernel;
-      l.split_asked = l.split_granted = 1;
-      l.x_elem = l.y_elem = 4;
-      rec.launches.push_back(l);
-      return rec.launches.back();
-    };
-    auto add = [&](clasfv_plan_launch_t& l, int buffer, int role, int write, int64_t offset, int64_t bytes) {
-      if (l.n_ranges < CLASFV_PLAN_MAX_RANGES) l.range[l.n_ranges++] = {buffer, role, write, 0, offset, bytes};
-    };
-    // a range of the arena: the buffer is the one its first byte lies in
-    auto add_arena = [&](clasfv_plan_launch_t& l, const void* p, int role, int write, int64_t bytes) {
-      const int64_t off = reinterpret_cast<const char*>(p) - arena;
-      int b = 0;
-      while (b + 1 < NBUF && off >= (int64_t)L.off[b + 1]) ++b;
-      add(l, b, role, write, off, bytes);
-    };
-    const CallerOffsets at = caller_offsets(n0, T, H, W);
-    const int64_t clip = (int64_t)T * H * W;
-    auto pack = [&](void* xin) {
-      clasfv_plan_launch_t& l = launch(0, CLASFV_PLAN_PACK, -1, "pack_input_kernel");
-      add(l, CLASFV_PLAN_EXT_CLIP, CLASFV_PLAN_X, 0, (int64_t)at.x * 4, (int64_t)n * 3 * clip * 4);
-      add_arena(l, xin, CLASFV_PLAN_Y, 1, (int64_t)n * clip * 4 * 4);  // launch_pack_input: 3 + 1 fp32 channels
-      return (int)CLASFV_OK;
-    };
-    auto conv = [&](int stream, const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res,
-                    bool relu, const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
-      const KernelInfo* k = nullptr;
-      ConvBuilt cb{};
-      if (int rc = run_conv(c, xin, in, y, out, res, relu, nullptr, arena, x2, &k, h->tune, x_c8, y_c8, scratch,
-                            scratch_bytes, true, &cb))
-        return rc;
-      const ConvParams& p = cb.p;
-      const int xe = p.in_bf16 ? 2 : 4, ye = p.out_bf16 ? 2 : 4;
-      const int64_t vin = (int64_t)p.N * p.Ti * p.Hi * p.Wi, m = (int64_t)p.N * p.To * p.Ho * p.Wo;
-      const int64_t part = (int64_t)p.n_split * m * p.Cout * 4;
-      const bool split = p.n_split > 1;
-      clasfv_plan_launch_t& l = launch(stream, CLASFV_PLAN_CONV, conv_index(h, c), k->name);
-      auto describe = [&](clasfv_plan_launch_t& d) {
-        d.split_asked = cb.split_asked, d.split_granted = split ? p.n_split : 1;
-        d.x_c8 = p.x_c8, d.y_c8 = p.y_c8, d.relu = p.relu, d.has_res = p.res != nullptr;
-        d.x_elem = xe, d.y_elem = ye;
-      };
-      auto epilogue = [&](clasfv_plan_launch_t& d) {  // what the launch that writes y addresses beside its sums
-        if (p.res) add_arena(d, p.res, CLASFV_PLAN_RES, 0, m * p.Cout * ye);
-        add_arena(d, p.y, CLASFV_PLAN_Y, 1, m * p.Cout * ye);
-      };
-      describe(l);
-      add_arena(l, p.x, CLASFV_PLAN_X, 0, vin * p.Cin * xe);
-      if (p.x2) add_arena(l, p.x2, CLASFV_PLAN_X2, 0, vin * p.Cin2 * xe);
-      if (!split) {
-        epilogue(l);
-        return (int)CLASFV_OK;
-      }
-      add_arena(l, p.part, CLASFV_PLAN_PART, 1, part);
-      clasfv_plan_launch_t& ssum = launch(stream, CLASFV_PLAN_SPLIT_SUM, conv_index(h, c), "split_sum_kernel");
-      describe(ssum);
-      add_arena(ssum, p.part, CLASFV_PLAN_PART, 0, part);
-      epilogue(ssum);
-      return (int)CLASFV_OK;
-    };
-    auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-                   const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
-      return conv(0, c, xin, in, y, out, res, relu, x2, x_c8, y_c8, scratch, scratch_bytes);
-    };
-    auto run_side = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* x2) {
-      launch(1, CLASFV_PLAN_FORK, -1, "");  // ev_fork recorded on s, awaited by the side stream
-      side_pending = true;
-      return conv(1, c, xin, in, y, out, nullptr, false, x2, 0, 0, nullptr, 0);
-    };
-    auto join = [&]() {
-      if (side_pending) launch(0, CLASFV_PLAN_JOIN, -1, "");  // ev_join recorded on the side stream, awaited by s
-      side_pending = false;
-      return (int)CLASFV_OK;
-    };
-    auto decode = [&](const float* const tp[4], const Shape5 tsh[4], void* idx) {
-      const DecParams d = decoder_params(h, tp, tsh, nullptr, nullptr, n, T, H, W, idx);
-      if (!decoder_addressable(d)) return fail(CLASFV_EBADSHAPE, "decoder_kernel: a tap has 2^31 floats or more");
-      const int64_t table = (int64_t)decoder_index_bytes(d.T, d.H, d.W);
-      clasfv_plan_launch_t& li = launch(0, CLASFV_PLAN_DEC_INDEX, -1, "decoder_index_kernel");
-      add_arena(li, d.idx, CLASFV_PLAN_IDX, 1, table);
-      clasfv_plan_launch_t& l = launch(0, CLASFV_PLAN_DECODER, -1, "decoder_kernel");
-      for (int i = 0; i < 4; ++i)
-        add_arena(l, d.tap[i].p, CLASFV_PLAN_TAP, 0, (int64_t)d.N * d.tap[i].T * d.tap[i].H * d.tap[i].W * 64 * 4);
-      add_arena(l, d.idx, CLASFV_PLAN_IDX, 0, table);
-      add(l, CLASFV_PLAN_EXT_SEG, CLASFV_PLAN_Y, 1, (int64_t)at.seg * 4, (int64_t)d.N * 2 * clip * 4);
-      add(l, CLASFV_PLAN_EXT_MOTION, CLASFV_PLAN_Y, 1, (int64_t)at.mot * 4, (int64_t)d.N * 4 * clip * 4);
-      return (int)CLASFV_OK;
-    };
-    return walk_network(h, L, arena, n, T, H, W, pack, run, run_side, join, decode);
+    return plan_sub_batch(h, rec, sub, n0, n, T, H, W, L);
   });
 }
 
@@ -1528,10 +1532,13 @@ int clasfv_set_kernel_variants(clasfv_t h, int flags) {
 
 int clasfv_get_kernel_variants(clasfv_t h) { return h ? h->tune.vflags : CLASFV_EINVAL; }
 
+// What the network's strides need of a clip: whole 8-frame and 16-pixel steps, at least one of each.
+static bool clip_shape_ok(int T, int H, int W) { return T >= 8 && H >= 16 && W >= 16 && !(T % 8 || H % 16 || W % 16); }
+
 // The plan of an engine of this dtype and these variants with every weight image clasfv_finalize would
 // upload marked present: no device is touched, and nothing of it may be launched.
 static int plan_only(clasfv_engine* e, int T, int H, int W, int dtype, int variants) {
-  if (T < 8 || H < 16 || W < 16 || T % 8 || H % 16 || W % 16)
+  if (!clip_shape_ok(T, H, W))
     return fail(CLASFV_EBADSHAPE, "shape must satisfy T % 8 == 0, H % 16 == 0, W % 16 == 0");
   if (dtype != CLASFV_DTYPE_FP32 && dtype != CLASFV_DTYPE_BF16) return fail(CLASFV_EINVAL, "unknown dtype");
   if (variants & ~kVariantMask) return fail(CLASFV_EINVAL, "unknown kernel-variant bit");
@@ -1589,7 +1596,7 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   if (!h->ready) return fail(CLASFV_ENOTREADY, "clasfv_finalize has not been called");
   if (!x || !seg || !mot) return fail(CLASFV_EINVAL, "null tensor");
   if (N < 1) return fail(CLASFV_EINVAL, "N must be >= 1");
-  if (T < 8 || H < 16 || W < 16 || T % 8 || H % 16 || W % 16)
+  if (!clip_shape_ok(T, H, W))
     return fail(CLASFV_EBADSHAPE, "shape must satisfy T % 8 == 0, H % 16 == 0, W % 16 == 0 (got T=" +
                                       std::to_string(T) + " H=" + std::to_string(H) + " W=" + std::to_string(W) + ")");
   // The largest batch every kernel of the network can address in one pass (per handle state and clip
@@ -1636,29 +1643,27 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
   // a decoder projection on the side stream once its tap is complete on s (timed with its own events;
   // with kernel timing on, the layer4 launches on s run concurrently with these, so their event
   // intervals overlap: the per-kernel sums of a forward exceed its wall time by about the overlap)
-  auto run_side = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* x2) {
+  auto run_side = [&](const ConvCall& cc, Shape5& out) {
     HIP_TRY(hipEventRecord(cx->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(cx->side, cx->ev_fork, 0));
     side_join.pending = true;
     const int e0 = h->ktime ? tick(h, cx->side) : -1;
-    const KernelInfo* k = nullptr;
-    log_begin(h);
-    int rc_ = run_conv(c, xin, in, y, out, nullptr, false, cx->side, h->zero, x2, &k, h->tune);
-    log_end(h, conv_index(h, c));
-    if (!rc_ && e0 >= 0) {
+    ConvBuilt b;
+    if (int rc_ = run_conv(h, cc, cx->side, b)) return rc_;
+    out = b.out;
+    if (e0 >= 0) {
       const int e1 = tick(h, cx->side);
-      if (e1 >= 0) h->recs.push_back({k->name, conv_gflop(c, out), k->xgflop(c, out), e0, e1});
+      const Conv& c = *cc.conv;
+      if (e1 >= 0) h->recs.push_back({b.kernel->name, conv_gflop(c, out), b.kernel->xgflop(c, out), e0, e1});
     }
-    return rc_;
+    return (int)CLASFV_OK;
   };
-  auto run = [&](const Conv& c, const void* xin, const Shape5& in, void* y, Shape5& out, const void* res, bool relu,
-                 const void* x2, int x_c8, int y_c8, void* scratch, size_t scratch_bytes) {
-    const KernelInfo* k = nullptr;
-    log_begin(h);
-    int rc_ = run_conv(c, xin, in, y, out, res, relu, s, h->zero, x2, &k, h->tune, x_c8, y_c8, scratch, scratch_bytes);
-    log_end(h, conv_index(h, c));
-    if (!rc_) timed(k->name, conv_gflop(c, out), k->xgflop(c, out));
-    return rc_;
+  auto run = [&](const ConvCall& cc, Shape5& out) {
+    ConvBuilt b;
+    if (int rc_ = run_conv(h, cc, s, b)) return rc_;
+    out = b.out;
+    timed(b.kernel->name, conv_gflop(*cc.conv, out), b.kernel->xgflop(*cc.conv, out));
+    return (int)CLASFV_OK;
   };
   auto join = [&]() {
     HIP_TRY(side_join.join());
@@ -1755,9 +1760,7 @@ int clasfv_fill_workspace(clasfv_t h, int byte, void* stream) {
   if (!h) return fail(CLASFV_EINVAL, "null handle");
   if (byte < 0 || byte > 255) return fail(CLASFV_EINVAL, "fill byte must be in [0, 255]");
   hipStream_t s = (hipStream_t)stream;
-  clasfv_engine::Ctx* cx = nullptr;
-  for (auto* c : h->ctxs)
-    if (c->stream == s) cx = c;
+  const clasfv_engine::Ctx* cx = find_ctx(h, s);
   if (!cx || !cx->arena) return fail(CLASFV_EINVAL, "no workspace exists for this stream yet");
   DEVICE_GUARD(h->device);
   HIP_TRY(hipMemsetAsync(cx->arena, byte, cx->arena_bytes, s));
@@ -1766,9 +1769,7 @@ int clasfv_fill_workspace(clasfv_t h, int byte, void* stream) {
 
 int clasfv_workspace_view(clasfv_t h, void* stream, void** base, int64_t* bytes) {
   if (!h) return fail(CLASFV_EINVAL, "null handle");
-  const clasfv_engine::Ctx* cx = nullptr;
-  for (const auto* c : h->ctxs)
-    if (c->stream == (hipStream_t)stream) cx = c;
+  const clasfv_engine::Ctx* cx = find_ctx(h, (hipStream_t)stream);
   if (!cx || !cx->arena) return fail(CLASFV_EINVAL, "no workspace exists for this stream yet");
   if (base) *base = cx->arena;
   if (bytes) *bytes = (int64_t)cx->arena_bytes;
@@ -1814,13 +1815,10 @@ int clasfv_run_conv(clasfv_t h, int i, const void* x, int N, int T, int H, int W
     return fail(CLASFV_EINVAL, "input smaller than the kernel");
   DEVICE_GUARD(h->device);
   const Shape5 in{N, T, H, W, c->cin_p};
-  Shape5 out;
-  const KernelInfo* k = nullptr;
-  log_begin(h);
-  int rc = run_conv(*c, x, in, y, out, res, relu != 0, (hipStream_t)stream, h->zero, x2, &k, h->tune, x_c8, y_c8,
-                    scratch_bytes ? scratch : nullptr, (size_t)scratch_bytes);
-  log_end(h, i);
-  if (kernel_name) *kernel_name = k ? k->name : "";
+  const ConvCall cc{c, in, x, x2, res, y, relu != 0, x_c8, y_c8, scratch_bytes ? scratch : nullptr, (size_t)scratch_bytes};
+  ConvBuilt b;
+  const int rc = run_conv(h, cc, (hipStream_t)stream, b);
+  if (kernel_name) *kernel_name = b.kernel ? b.kernel->name : "";
   return rc;
 }
 

@@ -106,11 +106,7 @@ class Engine:
     def set_variants(self, *names):
         """Kernel variants for A/B tests (CLASFV_VARIANT_*; e.g. "no_winograd"); no names = the
         product kernels. Returns the previous names. Call load() afterwards if no_winograd changed."""
-        flags = 0
-        for n in names:
-            if n not in _lib.VARIANTS:
-                raise ValueError(f"unknown kernel variant {n!r}: {sorted(_lib.VARIANTS)}")
-            flags |= _lib.VARIANTS[n]
+        flags = variant_flags(names)
         old = self.lib.clasfv_get_kernel_variants(self.h)
         _lib.check(self.lib.clasfv_set_kernel_variants(self.h, flags), "clasfv_set_kernel_variants")
         return tuple(n for n, b in _lib.VARIANTS.items() if old & b)

@@ -250,6 +250,62 @@ def test_single_variant_plan(dtype, shape, variant):
     audit_real(dtype, shape[0], shape[1:], (variant,))
 
 
+# variant bit -> the kernels it switches off, by reported name: written here from include/clasfv.h's comments,
+# not read from the engine's kernel table. A bit that is not listed switches no conv kernel off (it chooses a
+# form inside a launcher, a layout, or the decoder's arithmetic).
+_W4R, _W4W, _W4 = "conv_wino4r", "conv_wino4w", "conv_wino4"
+SWITCHES_OFF = {
+    "no_wino4r": {_W4R},
+    "no_wino4w": {_W4R, _W4W},
+    "no_wino4": {_W4R, _W4W, _W4},
+    "no_wino_patch": {"conv_wino_q"},
+    "no_stem_bf16": {"conv_stem_bf16"},
+    "no_stem_x3": {"conv_stem_x3"},
+    "no_proj_x3": {"conv_proj_x3"},
+    "no_dma_x3": {"conv_proj_x3", "conv_dma_x3"},
+    "no_patch32": {"conv_patch32_bf16"},
+    "no_twalk": {"conv_twalk_bf16"},
+    "no_patch_bf16": {"conv_patch32_bf16", "conv_twalk_bf16", "conv_patch_bf16"},
+    "no_dma_w": {"conv_dma_w"},
+    "no_dma_buf": {"conv_dma_w"},  # conv_dma_w has a buffer-offset form only: without it, conv_dma's pointer form
+    "no_winograd": {_W4R, _W4W, _W4, "conv_wino_q", "conv_wino", "conv_winot"},
+}
+SWITCH_SHAPES = (SMALL, RAGGED, CLIP, (1, 64, 224, 224))
+# (variants, the variants of the plan to compare with): every single bit against the product plan, and
+# no_wino_patch below no_wino4, where conv_wino_q is what the F(4x4) kernels' convs fall to
+SWITCH_CASES = [((v,), ()) for v in _variant_names()] + [(("no_wino4", "no_wino_patch"), ("no_wino4",))]
+
+
+def conv_kernels(p):
+    """conv index -> kernel name of a one-sub-batch plan."""
+    return {l["conv"]: l["kernel"] for l in p["launches"] if l["kind"] == "conv"}
+
+
+@pytest.mark.parametrize("variants,base", SWITCH_CASES, ids=lambda v: "+".join(v) or "product")
+def test_a_variant_bit_removes_exactly_its_kernels(variants, base):
+    """No conv of the variant's plan runs on a kernel the bit switches off, and every conv whose kernel differs
+    from the base plan's ran on a switched-off kernel there: the bit moves its own kernels' convs and no other."""
+    off = set().union(*(SWITCHES_OFF.get(v, set()) for v in set(variants) - set(base)))
+    changed = {}
+    for dtype in DTYPES:
+        for shape in SWITCH_SHAPES:
+            was, now = (conv_kernels(plan(dtype, shape[0], shape[1:], v)) for v in (base, variants))
+            assert sorted(was) == sorted(now) == list(range(41))
+            assert not off & set(now.values()), (dtype, shape, sorted(off & set(now.values())))
+            moved = {i: (was[i], now[i]) for i in was if was[i] != now[i]}
+            assert all(a in off for a, _ in moved.values()), (dtype, shape, moved)
+            changed[dtype, shape] = moved
+    if not off:
+        return
+    if variants == ("no_wino_patch",):  # the product's 1x3x3 convs are on the F(4x4) kernels: nothing to move
+        assert not any(changed.values())
+    else:
+        assert any(changed.values()), "the bit switches kernels off that no plan here uses"
+    if base:  # below no_wino4 the same bit moves conv_wino_q's convs to conv_wino, at every shape that has some
+        for shape in (SMALL, RAGGED, CLIP):
+            assert set(changed["fp32", shape].values()) == {("conv_wino_q", "conv_wino")}, shape
+
+
 def test_which_convs_split():
     """The product clip: layer4's four temporal convs (they read MID, and MID has room past their input at
     every batch) split four ways; no other conv asks, the 7x7 spatial convs 30, 33 and 35 on conv_dma_x3
