@@ -88,6 +88,9 @@ SIGNATURES = {
     "clasfv_track": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
                              c_int, _P, _P]),
     "clasfv_lv_geometry": (c_int, [_P, c_int64, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
+    "clasfv_render_workspace_bytes": (c_int64, []),
+    "clasfv_render_annotated": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_int, ctypes.c_double, _P, _P, _P]),
 }
 
 ABI_VERSION = 3  # CLASFV_ABI_VERSION of include/clasfv.h these signatures describe

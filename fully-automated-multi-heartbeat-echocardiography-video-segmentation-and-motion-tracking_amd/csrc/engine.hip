@@ -22,6 +22,7 @@
 #include "common.h"
 #include "lvgeom.h"
 #include "plumbing.h"
+#include "render.h"
 #include "track.h"
 
 namespace {
@@ -1971,6 +1972,48 @@ int clasfv_lv_geometry(const uint8_t* masks, int64_t F, int H, int W, int label,
   if ((int64_t)H * W > CLASFV_LV_MAX_PIXELS)
     return fail(CLASFV_EBADSHAPE, "the frame is kept in LDS: H * W must be <= 162816");
   HIP_TRY(launch_lv_geometry(masks, F, H, W, label, sy, sx, area, geom, (hipStream_t)stream));
+  return CLASFV_OK;
+}
+
+int64_t clasfv_render_workspace_bytes(void) { return CLASFV_RENDER_WORKSPACE_BYTES; }
+
+int clasfv_render_annotated(const float* video, const uint8_t* masks, const uint8_t* truth, int T, int H, int W,
+                            const double* volume, int64_t volume_stride, const uint8_t* title, int first, int count,
+                            int Hp, int Wo, int Ht, int Hs, int label, double thickness, void* workspace,
+                            uint8_t* out, void* stream) {
+  if (!video || !masks || !volume || !workspace || !out) return fail(CLASFV_EINVAL, "bad argument (null pointer)");
+  if (T < 1 || H < 1 || W < 1 || Hp < 1 || Wo < 1 || Ht < 0 || Hs < 0)
+    return fail(CLASFV_EINVAL, "bad argument (T, H, W, Hp and Wo must be >= 1, Ht and Hs >= 0)");
+  if (count < 1) return fail(CLASFV_EINVAL, "bad argument (count must be >= 1)");
+  if (first < 0 || first >= T || count > T - first)
+    return fail(CLASFV_EINVAL, "bad argument (the frames [first, first + count) must lie in [0, T))");
+  if (label < 0 || label > 255) return fail(CLASFV_EINVAL, "bad argument (label must be in [0, 255])");
+  if (!(isfinite(thickness) && thickness >= 0.0))
+    return fail(CLASFV_EINVAL, "bad argument (the thickness must be finite and not negative)");
+  if (volume_stride < 1) return fail(CLASFV_EINVAL, "bad argument (volume_stride must be >= 1)");
+  if (((uintptr_t)volume | (uintptr_t)workspace) & 7)
+    return fail(CLASFV_EINVAL, "bad argument (volume_dev and workspace_dev must be 8-byte aligned)");
+  const uint64_t frame = (uint64_t)(Hp + (int64_t)Ht + Hs) * (uint64_t)Wo * 3, total = frame * (uint64_t)count;
+  if ((uint64_t)H * W >> 31 || frame >> 32 || total >> 32)
+    return fail(CLASFV_EBADSHAPE, "the output of one call must be below 2^32 bytes and H * W below 2^31");
+  const uint64_t thw = (uint64_t)T * H * W;
+  if (thw > (1ull << 60) / 12 || (uint64_t)volume_stride > (1ull << 60) / ((uint64_t)T * 8))
+    return fail(CLASFV_EBADSHAPE, "the inputs are past what 64-bit offsets address");
+  const uintptr_t o0 = (uintptr_t)out;
+  auto overlaps = [&](const void* p, uint64_t bytes) {
+    const uintptr_t i0 = (uintptr_t)p;
+    return p && bytes && i0 < o0 + total && o0 < i0 + bytes;
+  };
+  if (overlaps(video, thw * 12) || overlaps(masks, thw) || overlaps(truth, thw) ||
+      overlaps(volume, ((uint64_t)(T - 1) * (uint64_t)volume_stride + 1) * 8) ||
+      overlaps(title, (uint64_t)Ht * Wo * 3) || overlaps(workspace, CLASFV_RENDER_WORKSPACE_BYTES))
+    return fail(CLASFV_EINVAL, "out overlaps an input or the workspace");
+  RenderParams p;
+  p.video = video, p.masks = masks, p.truth = truth, p.volume = volume, p.title = title;
+  p.workspace = (double*)workspace, p.out = out, p.vstride = volume_stride;
+  p.T = T, p.H = H, p.W = W, p.first = first, p.count = count, p.Hp = Hp, p.Wo = Wo, p.Ht = Ht, p.Hs = Hs;
+  p.label = label, p.thickness = thickness;
+  HIP_TRY(launch_render_annotated(p, (hipStream_t)stream));
   return CLASFV_OK;
 }
 

@@ -408,6 +408,57 @@ int clasfv_track(const float* img_dev, int N, int C, int H, int W, const float* 
 int clasfv_lv_geometry(const uint8_t* masks_dev, int64_t F, int H, int W, int label, double sy, double sx,
                        int32_t* area_dev, double* geom_dev, void* stream);
 
+/* ---- annotated video (src/visualization_utils.py:346-437, 476-539) ------------------------------ */
+/* Frames [first, first + count) of make_annotated_gif's video for a T-frame clip, as out_dev
+ * (count, Hp + Ht + Hs, Wo, 3) uint8 RGB, dense; out_dev needs no alignment. New exports only: the ABI
+ * revision is unchanged. A frame is three bands, top to bottom; frame i depends on (T, i) and the inputs
+ * only, not on first, count or its place in the call.
+ *
+ * Overlay pane, Hp x Wo: echonet_overlay(gray, seg, vis=False) resized to nearest. From video_dev (3,T,H,W)
+ * float32, g = (v0 * 0.2989 + v1 * 0.5870) + v2 * 0.1140 in float64, each product and sum rounded (no FMA).
+ * R = G = B = g; a pixel of masks_dev (T,H,W) uint8 that equals `label` has R = G = g + 0.3
+ * (labColorMap_EchoNet[1]). With truth_dev (T,H,W) uint8 (may be NULL) the pane is the reference's
+ * difference image I_gt instead: R = G = g + 0.3 where prediction == label and truth != label, B = g + 0.3
+ * where prediction != label and truth == label. A channel x becomes the byte floor(255 * clip(x, 0, 1)), a
+ * NaN the byte 0: truncation is this project's rule (the reference hands its float frames to matplotlib and
+ * imagemagick, a path that is not reproducible pixel for pixel and is not the target). Pane pixel (r, c)
+ * shows source pixel (min(floor(r * ify), H - 1), min(floor(c * ifx), W - 1)) with
+ * ify = 1.0 / ((double)Hp / H), ifx = 1.0 / ((double)Wo / W): INTER_NEAREST as OpenCV's source defines it
+ * (the pane is pinned to this rule, not to a cv2 build). Hp and Wo are free, downscaling included; the
+ * reference uses Hp = Wo = 553.
+ *
+ * Title band, Ht x Wo: a copy of title_dev (Ht,Wo,3) uint8, black when title_dev is NULL. Ht may be 0.
+ *
+ * Curve strip, Hs x Wo (Hs may be 0): the volume curve up to frame i in lime green (50, 205, 50) on black,
+ * on the reference's axes: x spans [0, T + 1] over the Wo columns, y spans [vmin - 100, vmax + 100] over the
+ * Hs rows, upward, vmin and vmax the least and largest finite volume of the WHOLE video (none finite: a
+ * black strip). volume k is volume_dev[k * volume_stride] (doubles; a clasfv_lv_geometry output is read in
+ * place with geom_dev + 11 and stride CLASFV_LV_STRIDE). All in float64, every operation rounded:
+ *   S = (double)(T + 1) / Wo, yhi = vmax + 100, sy = (double)Hs / (yhi - (vmin - 100)), h = thickness / 2.
+ *   Column x of frame i covers the samples [A, B], A = x * S, B = min((x + 1) * S, i); nothing unless A <= B.
+ *   For every k from floor(A) to min(ceil(B) - 1, i - 1) with volume k and volume k + 1 both finite:
+ *     ta = max(k, A), tb = min(k + 1, B), dv = v[k + 1] - v[k],
+ *     va = v[k] + (ta - k) * dv, vb = v[k] + (tb - k) * dv, ya = (yhi - va) * sy, yb = (yhi - vb) * sy,
+ *     top = min(ya, yb) - h, bot = max(ya, yb) + h (min(p, q) = p < q ? p : q, max likewise);
+ *     row r is lime iff r + 1 > top and r <= bot for some such k ([r, r + 1) meets [top, bot]).
+ * So a segment with a NaN or infinite end is not drawn, frame 0 has an empty strip, several samples per column
+ * (T + 1 > Wo) are legal and nothing is anti-aliased.
+ *
+ * workspace_dev: caller-owned device scratch of clasfv_render_workspace_bytes() bytes (vmin and vmax, found
+ * on the device by a one-workgroup reduction before the frames), used in stream order: concurrent calls on
+ * different streams need different workspaces. Stream-ordered, two launches; no synchronisation, no handle;
+ * the volumes never visit the host. CLASFV_EINVAL, before any HIP call, for a null video_dev, masks_dev,
+ * volume_dev, workspace_dev or out_dev; T, H, W, Hp or Wo < 1, Ht or Hs < 0; count < 1 or frames outside
+ * [0, T); label outside [0, 255]; a thickness that is negative or not finite; volume_stride < 1; volume_dev
+ * or workspace_dev not 8-byte aligned; out_dev overlapping an input or the workspace. CLASFV_EBADSHAPE when
+ * the output of the call has 2^32 bytes or more (pixel indices are 32-bit: render the video in chunks of
+ * frames, which gives the same bytes) or H * W >= 2^31. */
+int64_t clasfv_render_workspace_bytes(void);
+int clasfv_render_annotated(const float* video_dev, const uint8_t* masks_dev, const uint8_t* truth_dev, int T,
+                            int H, int W, const double* volume_dev, int64_t volume_stride,
+                            const uint8_t* title_dev, int first, int count, int Hp, int Wo, int Ht, int Hs,
+                            int label, double thickness, void* workspace_dev, uint8_t* out_dev, void* stream);
+
 /* ---- preprocessing (motion_segment.py:96-106, src/echonet_dataset.py:38-50) --------------------- */
 /* frames_dev (T,Hs,Ws,3) uint8 RGB -> out_dev (3,T,H,W) float32, resized as
  * F.interpolate(size=(T,H,W), mode="trilinear", align_corners=True) on the (1,3,T,Hs,Ws) float

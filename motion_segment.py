@@ -9,6 +9,9 @@ an error. ``-d cuda`` / ``cuda:i`` pick the GPU.
 Extra opt-in flags: ``--synthetic-weights SEED`` with ``--synthetic-recipe echo|random`` (seeded
 weights when no checkpoint is available offline), ``--batch-size`` (clips per forward call) and
 ``--no-strict-reference`` (fuse_utils.segment_a_video_with_fusion(strict_reference=False)).
+``-c gif`` (and ``all``) writes ``<name>_annotated.gif``, the reference's annotated video (LV overlay, title,
+volume curve), rendered on the device (clasfv_amd.render) and encoded by PIL; without PIL the frames are
+written as ``<name>_annotated.npy``. ``-c volume_curve`` (not part of ``all``) pickles the per-frame curve.
 Video input: any file OpenCV can decode if cv2 is installed (as the reference), or ``.npy`` holding
 (T,H,W,3) uint8 RGB frames.
 """
@@ -36,8 +39,10 @@ def parse_args(argv=None):
     ap.add_argument("-o", "--output", required=False, type=str, help="Path to the output files", default=".")
     ap.add_argument("-v", "--verbose", action="store_true", help="Verbosity")
     ap.add_argument("-c", "--content", required=False, type=str,
-                    help="Content of the output: gif, binary, binary_video, all; also volume_curve (not part of "
-                         "all): the per-frame LV area, length, radii and volume", default="binary")
+                    help="Content of the output: gif (the annotated video <name>_annotated.gif: overlay, title and "
+                         "volume curve; <name>_annotated.npy when PIL is missing), binary, binary_video, all; also "
+                         "volume_curve (not part of all): the per-frame LV area, length, radii and volume",
+                    default="binary")
     ap.add_argument("--height", required=False, type=int, help="Height of image (pretrain model uses 112)", default=112)
     ap.add_argument("--width", required=False, type=int, help="Width of image (pretrain model uses 112)", default=112)
     ap.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED",
@@ -129,8 +134,18 @@ def main(argv=None):
     filename = args.path[args.path.rfind("/") + 1:args.path.rfind(".")]
     content = args.content.lower().split(",")
     if "gif" in content or "all" in content:
-        print("warning: annotated GIF output (src/visualization_utils.py:476-539) is not part of this engine; skipped",
-              file=sys.stderr)
+        # make_annotated_gif (src/visualization_utils.py:476-539) from the device masks and video: the frames
+        # are rendered by one kernel (render.annotate_video) and only the finished frames come to the host
+        from clasfv_amd import render
+        frames = render.annotate_video(video[:, :fused.shape[0]], fused).cpu().numpy()
+        try:
+            render.write_gif(frames, os.path.join(args.output, filename + "_annotated.gif"))
+        except RuntimeError as e:
+            if "PIL" not in str(e):
+                raise
+            print("notice: PIL (Pillow) is not installed: the annotated frames are written as "
+                  f"{filename}_annotated.npy ((T,H,W,3) uint8 RGB) instead of a GIF", file=sys.stderr)
+            np.save(os.path.join(args.output, filename + "_annotated.npy"), frames)
     if "binary" in content or "all" in content:
         for ed_index, es_index in edes_pairs:
             with open(os.path.join(args.output, filename + "_ED_Frame_{:d}_segmentation.pkl".format(ed_index)), "wb") as f:
