@@ -109,6 +109,8 @@ VARIANTS = {"no_winograd": 1, "no_wino_patch": 2, "winot_reference": 4, "no_c8":
             "no_patch32": 16384, "no_proj_x3": 32768, "no_wino4r": 65536,
             "no_dma_buf": 262144, "w4r_cached_stores": 524288,
             "patch32_cached_stores": 4194304, "no_dma_w": 16777216, "no_twalk": 67108864}
+# CLASFV_VARIANT_NO_DMA_X3_WIDE (a #define beside the enum): conv_dma_x3 never in its wide form; pass the bit itself
+NO_DMA_X3_WIDE = 268435456
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 _lib = None
 

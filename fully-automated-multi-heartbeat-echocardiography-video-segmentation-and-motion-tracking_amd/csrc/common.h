@@ -191,6 +191,8 @@ bool dma_x3_supported(const ConvParams& p);
 bool dma_w_ok(const ConvParams& p);
 int dma_x3_bn(int cout_p);
 hipError_t launch_dma_x3(const ConvParams& p, int bn, hipStream_t s);
+// whether launch_dma_x3 takes the wide form for p (256-voxel x 240-channel blocks, n_split decided)
+bool dma_x3_wide_ok(const ConvParams& p);
 void dma_x3_weight_image(const float* w, int cout_alloc, int Kp, uint16_t* out);
 size_t dma_x3_weight_elems(int cout_alloc, int Kp);
 // Split-K factor (ConvParams::n_split) for launch_winot (1: no split; per-clip shape only); the

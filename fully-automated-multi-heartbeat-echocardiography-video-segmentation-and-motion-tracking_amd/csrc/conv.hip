@@ -902,6 +902,191 @@ __global__ __launch_bounds__(256) void conv_dma_x3(ConvParams p, int n_tiles, Dm
 }
 
 // ---------------------------------------------------------------------------------------------
+// conv_dma_x3, wide form (tag N240; Cout % 240 == 0, Cin and Cin2 % 32 == 0, the buffer DMAs, no
+// split-K): one block covers 256 output voxels x 240 output channels. 240 and 480 are no multiples of
+// 128, so the form above runs them as 3 x 80 / 5 x 96 channels per 128-row M tile, and every N block
+// of an M tile repeats the same A-side work: the 9-tap strided gather of the fp32 A tile and its
+// split into three bf16 pieces (profiles/r05q_dma_x3_knockouts.txt on layer2's 64 -> 240 strided
+// conv: loop DMAs 25 %, split 14 % of the time). Here that work is done once per 240 channels.
+//  * 8 waves, one block per CU (two waves per SIMD, as two 4-wave blocks); wave w owns rows
+//    32 w .. 32 w + 31 (2 row tiles) x all 15 N tiles: 30 f32x4 accumulators;
+//  * ring stage = one 32-deep K block: A 256 rows x 128 B (the WR form's row layout and XOR swizzle),
+//    B 3 pieces x 240 rows x 64 B (the form above's); two stages = 154 KiB;
+//  * per K block and wave: 4 A reads, 2 splits, 45 B-piece reads, 180 MFMAs, one barrier.
+// K blocks and the six products of each run in the order of the form above, so every output element
+// sees the same sums: bit-identical. EF, KO: as above (KO 1, 2, 4, 16).
+struct N240 {};
+template <typename FORM, int EF, int KO = 0>
+__global__ __launch_bounds__(512) void conv_dma_x3(ConvParams p, int n_nblocks, DmaDivs dv) {
+  constexpr int NT = 15, BM = 256, BN = 16 * NT;
+  constexpr int A_INS = BM / 8, B_INS = 3 * NT;  // DMA instructions: A 8 rows x 128 B, B 16 rows x 64 B
+  constexpr int RA = A_INS / 8, B_PER = (B_INS + 7) / 8;  // per wave; B instruction w + 8 j past B_INS: none
+  constexpr int A_BYTES = A_INS * 1024;
+  constexpr int STAGE = A_BYTES + B_INS * 1024;
+  static_assert(2 * STAGE <= 160 * 1024, "two ring stages fit the CU's 160 KiB of LDS");
+  __shared__ __align__(16) char smem[2 * STAGE];
+
+  const float* x = reinterpret_cast<const float*>(p.x);
+  const float* x2 = reinterpret_cast<const float*>(p.x2);
+  const __bf16* w = reinterpret_cast<const __bf16*>(p.w);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // N blocks fastest: the blocks of one M tile are neighbours on one XCD
+  const int tile = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int tq = fdiv(tile, dv.nt);
+  const int m0 = tq * BM, n0 = (tile - tq * n_nblocks) * BN;
+  const int q = lane >> 4, l16 = lane & 15;
+  constexpr int G[4] = {0, 2, 3, 1};
+
+  const int npairs = p.Kp / 32;
+  const int adq = (lane & 7) ^ (lane >> 3);  // logical A slot this lane fetches (row % 8 = lane / 8)
+  unsigned a_vm[RA], a_bo[RA], a_bo2[RA];
+  const int padpix = (p.pt * p.Hi + p.ph) * p.Wi + p.pw;
+  const size_t vox = (size_t)p.N * p.Ti * p.Hi * p.Wi;
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(x - (size_t)padpix * p.Cin), (short)0, (int)((vox + padpix) * p.Cin * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t x2r = __builtin_amdgcn_make_buffer_rsrc(
+      x2 ? const_cast<float*>(x2) : nullptr, (short)0, x2 ? (int)(vox * p.Cin2 * 4) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<__bf16*>(w), (short)0, (int)((size_t)p.Cout * npairs * 192), 0x00020000);
+#pragma unroll
+  for (int j = 0; j < RA; ++j) {
+    int m = m0 + (wid * RA + j) * 8 + (lane >> 3);
+    const bool ok = m < p.M;
+    if (!ok) m = 0;
+    const int mw = fdiv(m, dv.wo), wo = m - mw * p.Wo;
+    const int mh = fdiv(mw, dv.ho), ho = mw - mh * p.Ho;
+    const int mt = fdiv(mh, dv.to), to = mh - mt * p.To;
+    const int dt = ok ? to * p.st - p.pt : -(1 << 20), dh = ho * p.sh - p.ph, dw = wo * p.sw - p.pw;
+    const int dpix = ((mt * p.Ti + dt) * p.Hi + dh) * p.Wi + dw;
+    unsigned vm = 0;
+    for (int kt = 0; kt < p.KT; ++kt)
+      for (int kh = 0; kh < p.KH; ++kh)
+        for (int kw = 0; kw < p.KW; ++kw) {
+          const int ti = dt + kt, hi = dh + kh, wi = dw + kw;
+          const bool v = ((unsigned)ti < (unsigned)p.Ti) & ((unsigned)hi < (unsigned)p.Hi) & ((unsigned)wi < (unsigned)p.Wi);
+          vm |= (v ? 1u : 0u) << ((kt * p.KH + kh) * p.KW + kw);
+        }
+    a_vm[j] = vm;
+    a_bo[j] = (unsigned)(dpix + padpix) * (unsigned)(p.Cin * 4) + 16u * (unsigned)adq;
+    a_bo2[j] = (unsigned)dpix * (unsigned)(p.Cin2 * 4) + 16u * (unsigned)adq;
+  }
+  const int drow = lane >> 2;
+  const int dq = (lane & 3) ^ G[(drow >> 2) & 3];
+  unsigned b_bo[B_PER];
+#pragma unroll
+  for (int j = 0; j < B_PER; ++j) {
+    const int idx = wid + 8 * j;  // B instruction: piece idx / NT, rows 16 (idx % NT) ..
+    const int pc = idx / NT, nr = idx - pc * NT;
+    b_bo[j] = idx < B_INS ? (unsigned)((pc * p.Cout + n0 + nr * 16 + drow) * 64 + 16 * dq) : 0x80000000u;
+  }
+  int c_c0 = 0, c_kt = 0, c_kh = 0, c_kw = 0, c_tap_pix = 0;
+  bool c_second = p.KT * p.KH * p.KW * p.Cin == 0;
+  auto issue = [&](int pair, int slot) {
+    char* stg = smem + slot * STAGE;
+    const bool second = c_second;
+    const int cin = second ? p.Cin2 : p.Cin;
+    const int c0 = c_c0, kt = c_kt, kh = c_kh, kw = c_kw, tap_pix = c_tap_pix;
+    c_c0 += 32;
+    if (c_c0 == cin) {
+      c_c0 = 0;
+      if (++c_kw == p.KW) {
+        c_kw = 0;
+        if (++c_kh == p.KH) {
+          c_kh = 0;
+          if (++c_kt == p.KT) c_kt = 0, c_second = true;
+        }
+      }
+      c_tap_pix = (c_kt * p.Hi + c_kh) * p.Wi + c_kw;
+    }
+    const unsigned tap = (unsigned)((kt * p.KH + kh) * p.KW + kw);
+    const unsigned soff = (unsigned)(tap_pix * cin + c0) * 4u;
+#pragma unroll
+    for (int j = 0; j < RA; ++j) {
+      const unsigned off = ((a_vm[j] >> tap) & 1u) ? (second ? a_bo2[j] : a_bo[j]) : 0x80000000u;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          second ? x2r : xr, (__attribute__((address_space(3))) void*)(stg + (wid * RA + j) * 1024), 16, off, soff, 0, 0);
+    }
+    const unsigned so = (unsigned)pair * (unsigned)(192 * p.Cout);
+#pragma unroll
+    for (int j = 0; j < B_PER; ++j) {
+      const int idx = wid + 8 * j;
+      if (j < B_PER - 1 || idx < B_INS) {  // wave-uniform
+        const unsigned bo = b_bo[j];
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            wr, (__attribute__((address_space(3))) void*)(stg + A_BYTES + idx * 1024), 16, bo, so, 0, 0);
+      }
+    }
+  };
+
+  f32x4 acc[2][NT];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (npairs > 0) issue(0, 0);
+  const int a_off = (wid * 32 + l16) * 128;
+  const int sa0 = (q ^ (l16 & 7)) * 16, sa1 = ((4 + q) ^ (l16 & 7)) * 16;
+  const int b_off = A_BYTES + l16 * 64 + (q ^ G[l16 >> 2]) * 16;
+  for (int k = 0; k < npairs; ++k) {
+    // stage k landed (this wave's DMAs, then every wave's); everyone is done with stage k - 1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr ((KO & 4) == 0)
+      if (k + 1 < npairs) issue(k + 1, (k + 1) & 1);
+    const char* st = smem + (k & 1) * STAGE;
+    bf16x8 ah[2], am[2], al[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const char* ar = st + a_off + i * 16 * 128;
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(ar + sa0);
+      const f32x4 a1 = *reinterpret_cast<const f32x4*>(ar + sa1);
+      if constexpr ((KO & 1) != 0) {
+        ah[i] = __builtin_bit_cast(bf16x8, a0);
+        am[i] = __builtin_bit_cast(bf16x8, a1);
+        al[i] = ah[i];
+      } else {
+        split3_bf16x8(a0, a1, ah[i], am[i], al[i]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      bf16x8 bh, bm, bl;
+      if constexpr ((KO & 2) != 0) {
+        bh = ah[0], bm = am[0], bl = al[0];
+      } else {
+        bh = *reinterpret_cast<const bf16x8*>(st + b_off + j * 1024);
+        bm = *reinterpret_cast<const bf16x8*>(st + b_off + (NT + j) * 1024);
+        bl = *reinterpret_cast<const bf16x8*>(st + b_off + (2 * NT + j) * 1024);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        f32x4 c = acc[i][j];
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah[i], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al[i], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, am[i], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, ah[i], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, am[i], c, 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah[i], c, 0, 0, 0);
+      }
+    }
+  }
+  if constexpr ((KO & 16) != 0) {
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) sum += acc[i][j][0] + acc[i][j][3];
+    if (sum == 1234.5f) reinterpret_cast<float*>(p.y)[tid] = sum;
+    return;
+  }
+  epilogue<2, NT, EF, false>(p, acc, m0 + wid * 32, n0, q, l16);
+}
+
+// ---------------------------------------------------------------------------------------------
 // conv_proj_x3 (round 4): the decoder's 1x1x1 tap projections (P01 = W0 f_stem + W1 f_layer1, P2,
 // P3: 64 output channels, K = 128 / 128 / 256) as a persistent split-bf16 GEMM. On conv_dma_x3 a
 // 128-voxel block ran only K / 32 = 4 ring steps, so its prologue and epilogue latencies dominated
@@ -1333,6 +1518,29 @@ hipError_t launch_dma_x3_t(const ConvParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// conv_dma_x3's wide form (256 voxels x 240 channels per block): a rule over the conv's own shape,
+// never the batch -- Cout a multiple of 240, every 32-deep K block inside one tap of one input, one K
+// range, no residual (no 240-channel conv of the network adds one, and its row loads beside 30
+// accumulators and 15 bias vectors would spill) -- and the buffer-DMA limits, past which the form above
+// takes the batch, bit for bit the same (CLASFV_VARIANT_NO_DMA_X3_WIDE: the form above everywhere)
+bool dma_x3_wide_ok_(const ConvParams& p) {
+  if (p.vflags & CLASFV_VARIANT_NO_DMA_X3_WIDE) return false;
+  return dma_x3_supported(p) && p.Cout % 240 == 0 && p.n_split <= 1 && !p.res && p.Cin % 32 == 0 &&
+         (!p.x2 || p.Cin2 % 32 == 0) && p.Kp % 32 == 0 && dma_x3_buf_ok(p, p.Cout);
+}
+
+template <int KO = 0>
+hipError_t launch_dma_x3_wide(const ConvParams& p, hipStream_t s) {
+  const int mt = (p.M + 255) / 256, nb = p.Cout / 240;
+  const DmaDivs dv{fast_div(p.Wo), fast_div(p.Ho), fast_div(p.To), fast_div(nb)};
+  const dim3 grid(mt * nb);
+  if (p.relu)
+    CLASFV_LAUNCH((conv_dma_x3<N240, 2, KO>), grid, dim3(512), 0, s, p, nb, dv);
+  else
+    CLASFV_LAUNCH((conv_dma_x3<N240, 0, KO>), grid, dim3(512), 0, s, p, nb, dv);
+  return hipGetLastError();
+}
+
 template <int NT>
 hipError_t launch_stem(const ConvParams& p, hipStream_t s) {
   if (p.Cin != 4 || p.KT != 1 || p.KH != 7 || p.KW != 7) return hipErrorInvalidValue;  // conv_stem_f32's geometry
@@ -1504,6 +1712,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 }  // namespace
 
 bool dma_w_ok(const ConvParams& p) { return dma_w_ok_(p); }
+bool dma_x3_wide_ok(const ConvParams& p) { return dma_x3_wide_ok_(p); }
 
 #ifdef CLASFV_KNOCKOUTS
 hipError_t launch_dma_bf16_ko(const ConvParams& p, int bn, int ko, hipStream_t s) { return dma_bf16_ko(p, bn, ko, s); }
@@ -1554,6 +1763,7 @@ int dma_x3_bn(int cout_p) {
 
 hipError_t launch_dma_x3(const ConvParams& p, int bn, hipStream_t s) {
   if (!dma_x3_supported(p)) return hipErrorInvalidValue;
+  if (dma_x3_wide_ok(p)) return launch_dma_x3_wide(p, s);
   switch (bn) {
     case 16: return launch_dma_x3_t<2, 1, 2>(p, s);
     case 32: return launch_dma_x3_t<2, 2, 2>(p, s);
@@ -1603,7 +1813,7 @@ static hipError_t dma_x3_ko_t(const ConvParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 // conv_dma_x3 knock-outs (KO bits of conv_dma_x3; + 32: the BUF form) at MT 2, 2 stages, the ReLU
-// epilogue, N tile 16 nt
+// epilogue, N tile 16 nt; nt = 15: the wide form (KO 1, 2, 4, 16)
 hipError_t launch_dma_x3_ko(const ConvParams& p, int nt, int ko, hipStream_t s) {
   if (!dma_x3_supported(p) || p.res || !p.relu || p.y_c8 || p.n_split > 1) return hipErrorInvalidValue;
 #define DX3KO(N)                                       \
@@ -1625,6 +1835,14 @@ hipError_t launch_dma_x3_ko(const ConvParams& p, int nt, int ko, hipStream_t s) 
   if (nt == 5) DX3KO(5)
   if (nt == 8) DX3KO(8)
 #undef DX3KO
+  if (nt == 15 && dma_x3_wide_ok(p))  // the wide form (always the buffer DMAs: ko and ko + 32 alike)
+    switch (ko & 31) {
+      case 0: return launch_dma_x3_wide<0>(p, s);
+      case 1: return launch_dma_x3_wide<1>(p, s);
+      case 2: return launch_dma_x3_wide<2>(p, s);
+      case 4: return launch_dma_x3_wide<4>(p, s);
+      case 16: return launch_dma_x3_wide<16>(p, s);
+    }
   return hipErrorInvalidValue;
 }
 #endif

@@ -181,6 +181,7 @@ constexpr VariantSwitch kVariants[] = {
     {CLASFV_VARIANT_PATCH32_CACHED_STORES, "CLASFV_PATCH32_CACHED_STORES", false},
     {CLASFV_VARIANT_NO_DMA_W, "CLASFV_NO_DMA_W", false},
     {CLASFV_VARIANT_NO_TWALK, "CLASFV_NO_TWALK", false},
+    {CLASFV_VARIANT_NO_DMA_X3_WIDE, "CLASFV_NO_DMA_X3_WIDE", false},
 };
 
 // Kernel-variant flags and tuning overrides from the environment (read once, at clasfv_create).
@@ -663,10 +664,12 @@ double xg_patch32_bf16(const Conv& c, const Shape5& out) {  // 4 frames x 8x8-pi
          (double)c.Kp * 1e-9;
 }
 // conv_dma_x3: six bf16 products per product of the fp32 GEMM it computes (K padded to 32-deep pairs)
-double xg_dma_x3(const Conv& c, const Shape5& out) {
+// (M tiles of bm rows: 128, or the wide form's 256)
+double xg_dma_x3_rows(const Conv& c, const Shape5& out, double bm) {
   const double m = (double)out.n * out.t * out.h * out.w;
-  return 6 * 2.0 * (ceil(m / 128.0) * 128.0) * c.cout_p * (double)((c.Kp + 31) / 32 * 32) * 1e-9;
+  return 6 * 2.0 * (ceil(m / bm) * bm) * c.cout_p * (double)((c.Kp + 31) / 32 * 32) * 1e-9;
 }
+double xg_dma_x3(const Conv& c, const Shape5& out) { return xg_dma_x3_rows(c, out, 128.0); }
 double xg_gemm(const Conv& c, const Shape5& out) {  // launch_conv's kernels: 128-row M tiles
   const double m = (double)out.n * out.t * out.h * out.w;
   return 2.0 * (ceil(m / 128.0) * 128.0) * c.cout_p * (double)c.Kp * 1e-9;
@@ -856,6 +859,13 @@ struct ConvBuilt {
   int split_asked;  // the split-K factor the per-clip rule asked for (p.n_split is the one granted)
   int mt, bn;       // the implicit GEMMs' tile
 };
+
+// MFMA work of the launch decide_conv built: the kernel row's count, over conv_dma_x3's 256-row M tiles
+// where its launcher takes the wide form.
+double built_xgflop(const ConvBuilt& b) {
+  if (b.kernel->id == K_DMA_X3 && dma_x3_wide_ok(b.p)) return xg_dma_x3_rows(*b.conv, b.out, 256.0);
+  return b.kernel->xgflop(*b.conv, b.out);
+}
 
 // Decides how call cc runs on an engine with tuning tu and padding source zero_block: b is the kernel pick_kernel
 // chooses and its launch. A shape that kernel cannot address is refused (CLASFV_EBADSHAPE). Launches nothing.
@@ -1655,7 +1665,7 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     if (e0 >= 0) {
       const int e1 = tick(h, cx->side);
       const Conv& c = *cc.conv;
-      if (e1 >= 0) h->recs.push_back({b.kernel->name, conv_gflop(c, out), b.kernel->xgflop(c, out), e0, e1});
+      if (e1 >= 0) h->recs.push_back({b.kernel->name, conv_gflop(c, out), built_xgflop(b), e0, e1});
     }
     return (int)CLASFV_OK;
   };
@@ -1663,7 +1673,7 @@ int clasfv_forward(clasfv_t h, const float* x, int N, int T, int H, int W, float
     ConvBuilt b;
     if (int rc_ = run_conv(h, cc, s, b)) return rc_;
     out = b.out;
-    timed(b.kernel->name, conv_gflop(*cc.conv, out), b.kernel->xgflop(*cc.conv, out));
+    timed(b.kernel->name, conv_gflop(*cc.conv, out), built_xgflop(b));
     return (int)CLASFV_OK;
   };
   auto join = [&]() {

@@ -28,11 +28,14 @@ from .weights import DEFAULT_SEED, recipe_state_dict
 
 
 def variant_flags(names):
-    """CLASFV_VARIANT_* bits of variant names (an int passes through)."""
+    """CLASFV_VARIANT_* bits of variant names (an int passes through, alone or among the names)."""
     if isinstance(names, int):
         return names
     flags = 0
     for n in names:
+        if isinstance(n, int):
+            flags |= n
+            continue
         if n not in _lib.VARIANTS:
             raise ValueError(f"unknown kernel variant {n!r}: {sorted(_lib.VARIANTS)}")
         flags |= _lib.VARIANTS[n]

@@ -55,6 +55,11 @@ enum { CLASFV_FUSE_MAJORITY = 0, CLASFV_FUSE_SIMPLE = 1, CLASFV_FUSE_STAPLE = 2,
  * 16-vote one (A/B testing; results are identical). */
 #define CLASFV_FUSE_FORCE_GENERIC 0x100
 enum { CLASFV_DTYPE_FP32 = 0, CLASFV_DTYPE_BF16 = 1 };
+/* One more kernel-variant bit (CLASFV_NO_DMA_X3_WIDE in the environment; see the enum below):
+ * conv_dma_x3's 128-voxel x 80- / 96-channel blocks on the fp32 engines' 240- and 480-channel convs,
+ * instead of its wide form's 256-voxel x 240-channel blocks. The two are bit-identical; the bit serves
+ * A/B timing and the tests that hold one against the other. */
+#define CLASFV_VARIANT_NO_DMA_X3_WIDE 268435456
 
 /* Kernel-variant switches (A/B testing against the kernels each product kernel replaced; every
  * variant computes the same function -- NO_SPLIT_K the same sums in another fp32 summation order,

@@ -154,7 +154,7 @@ int main(int argc, char** argv) {
   // split-K into ko - 710 K ranges when >= 2
   void* wx3 = nullptr;
   for (int ko : kos)
-    if (!wino && !winot && !bf && ((ko >= 710 && ko < 720) || (ko >= 7200 && ko < 7264)) && !wx3) {
+    if (!wino && !winot && !bf && ((ko >= 710 && ko <= 720) || (ko >= 7200 && ko < 7264)) && !wx3) {
       std::vector<float> wf(nw);
       CK(hipMemcpy(wf.data(), p.w, nw * 4, hipMemcpyDeviceToHost));
       std::vector<uint16_t> img(dma_x3_weight_elems(Cout, p.Kp));
@@ -233,7 +233,11 @@ int main(int argc, char** argv) {
         CK(launch_dma_bf16_ko(q, bn, ko - 7300, s));
         return;
       }
-      if (ko >= 7200 && ko < 7264) {  // conv_dma_x3 knock-outs (KO = ko - 7200; + 32 the BUF form), N tile of CB_X3CFG's NT
+      if (ko == 720) {  // conv_dma_x3 as the engine launches it, but never the wide form (710: wide where its rule holds)
+        q.w = wx3;
+        q.vflags |= CLASFV_VARIANT_NO_DMA_X3_WIDE;
+        CK(launch_dma_x3(q, dma_x3_bn(Cout), s));
+      } else if (ko >= 7200 && ko < 7264) {  // conv_dma_x3 knock-outs (KO = ko - 7200; + 32 the BUF form), N tile of CB_X3CFG's NT (15: the wide form)
         q.w = wx3;
         const char* cfg = getenv("CB_X3CFG");
         int xm = 2, xn = dma_x3_bn(Cout) / 16, xs = 2;
