@@ -170,3 +170,36 @@ def stream_ptr(stream=None, device=None):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+def on_gpu(t, name, device=None, dtype=None):
+    """``t`` if it is a tensor on a GPU (on ``device`` and of ``dtype`` where given), else TypeError for
+    anything that is no tensor and ValueError naming the argument: the C ABI takes raw device pointers and
+    cannot tell what they point at, so this is the only place a host tensor or another dtype is caught.
+    Host comparisons only: no device work, no synchronisation."""
+    import torch
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a torch tensor on the GPU (the library reads its device pointer), not "
+                        f"{type(t).__name__}")
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype} (the library reads its bytes as that type), not {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be on the GPU (the library reads its device pointer), not on {t.device}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} must be on {device}, not on {t.device}")
+    return t
+
+
+def byte_span(t):
+    """[lo, hi) of the addresses a tensor's elements occupy (strides are not negative in torch); an empty
+    tensor spans nothing."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    last = sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def overlap(a, b):
+    """Whether the byte spans of two tensors intersect (the same tensor included)."""
+    (alo, ahi), (blo, bhi) = byte_span(a), byte_span(b)
+    return alo < ahi and blo < bhi and alo < bhi and blo < ahi

@@ -1934,9 +1934,28 @@ int clasfv_fuse_votes(const uint8_t* labels, int K, int T, int step, int H, int 
   return CLASFV_OK;
 }
 
+// Byte ranges of the warp entry points' tensors, for their overlap refusals. An empty range overlaps nothing.
+struct ByteSpan { uintptr_t lo, hi; };
+static ByteSpan dense_span(const void* p, uint64_t floats) {
+  return {(uintptr_t)p, (uintptr_t)p + floats * sizeof(float)};
+}
+// motion (N,2,H,W) with element strides m_sn, m_sc (either sign) and dense H * W planes
+static ByteSpan motion_span(const float* motion, int N, int H, int W, int64_t m_sn, int64_t m_sc) {
+  const int64_t dn = (int64_t)(N - 1) * m_sn;
+  const int64_t lo = (dn < 0 ? dn : 0) + (m_sc < 0 ? m_sc : 0), hi = (dn > 0 ? dn : 0) + (m_sc > 0 ? m_sc : 0);
+  return {(uintptr_t)(motion + lo), (uintptr_t)(motion + hi + (int64_t)H * W)};
+}
+static bool spans_overlap(const ByteSpan& a, const ByteSpan& b) {
+  return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi;
+}
+
 int clasfv_warp(const float* img, int N, int C, int H, int W, const float* motion, int64_t m_sn, int64_t m_sc,
                 float* out, void* stream) {
   if (!img || !motion || !out || N < 1 || C < 1 || H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad argument");
+  // every block reads img and motion while others write out
+  const ByteSpan o = dense_span(out, (uint64_t)N * C * H * W);
+  if (spans_overlap(o, dense_span(img, (uint64_t)N * C * H * W))) return fail(CLASFV_EINVAL, "out overlaps img");
+  if (spans_overlap(o, motion_span(motion, N, H, W, m_sn, m_sc))) return fail(CLASFV_EINVAL, "out overlaps motion");
   HIP_TRY(launch_warp(img, N, C, H, W, motion, m_sn, m_sc, out, (hipStream_t)stream));
   return CLASFV_OK;
 }
@@ -1945,6 +1964,15 @@ int clasfv_warp_backward(const float* grad_out, const float* img, int N, int C, 
                          int64_t m_sn, int64_t m_sc, float* grad_img, float* grad_motion, void* stream) {
   if (!grad_out || !img || !motion || (!grad_img && !grad_motion) || N < 1 || C < 1 || H < 1 || W < 1)
     return fail(CLASFV_EINVAL, "bad argument");
+  const ByteSpan in[3] = {dense_span(grad_out, (uint64_t)N * C * H * W), dense_span(img, (uint64_t)N * C * H * W),
+                          motion_span(motion, N, H, W, m_sn, m_sc)};
+  const ByteSpan gi = dense_span(grad_img, grad_img ? (uint64_t)N * C * H * W : 0);
+  const ByteSpan gm = dense_span(grad_motion, grad_motion ? (uint64_t)N * 2 * H * W : 0);
+  for (const ByteSpan& r : in) {
+    if (spans_overlap(gi, r)) return fail(CLASFV_EINVAL, "grad_img overlaps an input");
+    if (spans_overlap(gm, r)) return fail(CLASFV_EINVAL, "grad_motion overlaps an input");
+  }
+  if (spans_overlap(gi, gm)) return fail(CLASFV_EINVAL, "grad_img overlaps grad_motion");
   HIP_TRY(launch_warp_backward(grad_out, img, N, C, H, W, motion, m_sn, m_sc, grad_img, grad_motion,
                                (hipStream_t)stream));
   return CLASFV_OK;

@@ -96,31 +96,62 @@ def to_device_video(video, device):
 _TABLES = {}
 
 
-def _device_table(table, device):
+def check_clip_table(table, t, interpolate_last=True):
+    """ValueError unless every (shift, first_frame) of a clip table names 32 frames that clasfv_build_clips
+    can read from a t-frame video: 0 <= shift < t, first_frame >= 0, and first_frame + 32 within the pass's
+    length -- 32 * n_clips(t - shift) when the pass is resampled (interpolate_last and (t - shift) % 32 != 0),
+    else t - shift. The kernel trusts the table; an entry past that reads out of bounds."""
+    for i, entry in enumerate(table):
+        try:
+            shift, first = entry
+            ok = int(shift) == shift and int(first) == first
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"table[{i}] = {entry!r}: a pair of integers (shift, first_frame) expected")
+        if not 0 <= shift < t:
+            raise ValueError(f"table[{i}]: shift {shift} outside [0, {t}) of the {t}-frame video")
+        tk = t - shift
+        length = CLIP * n_clips(tk) if interpolate_last and tk % CLIP != 0 else tk
+        if first < 0 or first + CLIP > length:
+            raise ValueError(f"table[{i}]: frames [{first}, {first} + {CLIP}) outside the pass's {length} frames "
+                             f"(shift {shift}, {t}-frame video)")
+
+
+def _device_table(table, device, t=None, interpolate_last=True):
     """Device int32 copy of a clip table, cached: a fresh pageable host->device copy per call would
     make every video wait for the copy engine (and the host for the stream) before its clips build.
     A table is allocated on the stream that first asked for it and read by kernels on every stream that
     asks later, so each hand-out records the current stream on it: when the cache is emptied, the
     allocator keeps the block until the work queued on those streams so far has run (without that, a new
-    tensor could take the block while a kernel that has not started yet still reads the table)."""
-    key = (str(device), tuple(table))
-    t = _TABLES.get(key)
-    if t is None:
+    tensor could take the block while a kernel that has not started yet still reads the table).
+    With ``t`` (the video's frames) the host list is checked against it (check_clip_table) before it is
+    uploaded, on a cache miss only: the key holds t and interpolate_last, so a hit was checked for them.
+    Without ``t`` nothing is checked and the key has no t: the package never calls it so; the form is kept for
+    callers that upload a table of their own making and answer for it (the cache-eviction test does)."""
+    key = (str(device), tuple(table)) if t is None else (str(device), tuple(table), t, bool(interpolate_last))
+    tab = _TABLES.get(key)
+    if tab is None:
+        if t is not None:
+            check_clip_table(key[1], t, interpolate_last)
         if len(_TABLES) > 256:
             _TABLES.clear()
-        t = torch.tensor(np.asarray(table, np.int32).reshape(-1), device=device)
-        _TABLES[key] = t
-    t.record_stream(torch.cuda.current_stream(t.device))
-    return t
+        tab = torch.tensor(np.asarray(key[1], np.int32).reshape(-1), device=device)
+        _TABLES[key] = tab
+    tab.record_stream(torch.cuda.current_stream(tab.device))
+    return tab
 
 
 def build_clips(video_dev, table, interpolate_last=True):
-    """(n,3,32,H,W) clips on the device for a [(shift, first_frame)] table."""
+    """(n,3,32,H,W) clips on the device for a [(shift, first_frame)] table. ``video_dev``: a (3,T,H,W)
+    tensor on the GPU (any dtype and strides: converted); every table entry must lie inside the shifted,
+    resampled video (check_clip_table), else ValueError."""
+    _lib.on_gpu(video_dev, "video_dev")
     if video_dev.dim() != 4 or video_dev.shape[0] != 3:
-        raise ValueError(f"expected a (3,T,H,W) video, got {tuple(video_dev.shape)}")
-    video_dev = video_dev.to(torch.float32).contiguous()  # the ABI takes dense row-major buffers
+        raise ValueError(f"video_dev: expected a (3,T,H,W) video, got {tuple(video_dev.shape)}")
     _, t, h, w = video_dev.shape
-    tab = _device_table(table, video_dev.device)
+    tab = _device_table(table, video_dev.device, t, interpolate_last)  # a bad table is refused before any copy
+    video_dev = video_dev.to(torch.float32).contiguous()  # the ABI takes dense row-major buffers
     clips = torch.empty((len(table), 3, CLIP, h, w), device=video_dev.device, dtype=torch.float32)
     lib = _lib.load()
     _lib.check(lib.clasfv_build_clips(_lib.ptr(video_dev), t, h, w, _lib.ptr(tab), len(table), int(bool(interpolate_last)),
@@ -151,11 +182,50 @@ def run_model(model, clips, batch_size=None):
     return torch.cat(outs) if len(outs) > 1 else outs[0].contiguous()
 
 
+def check_fuse_votes_args(shape, step):
+    """ValueError unless (K,T,H,W) = ``shape`` and ``step`` are what clasfv_fuse_votes takes. Host arithmetic."""
+    if len(shape) != 4:
+        raise ValueError(f"labels (K,T,H,W) expected, got {tuple(shape)}")
+    k, t = shape[0], shape[1]
+    if not 1 <= k <= MAX_PASSES:
+        raise ValueError(f"labels: 1 to {MAX_PASSES} shifted passes are supported (got K = {k})")
+    if isinstance(step, bool) or int(step) != step or step < 1 or t - (step - 1) < 1:
+        raise ValueError(f"step {step!r} must be an integer >= 1 that leaves T - (step - 1) >= 1 of the {t} frames")
+
+
+def check_pass_labels_args(shape, clip0, t, step, margin=False):
+    """ValueError unless logits of ``shape`` hold every clip that clasfv_pass_labels reads for the passes
+    ``clip0``, ``t`` frames and ``step`` (pass k: clips [clip0[k], clip0[k] + n_clips(t - k * step))); returns
+    that clip count. Host arithmetic."""
+    k = len(clip0)
+    if k > MAX_PASSES:
+        raise ValueError(f"clip0: at most {MAX_PASSES} shifted passes are supported (got {k})")
+    want = (CLIP,) if margin else (2, CLIP)
+    if len(shape) != len(want) + 3 or tuple(shape[1:-2]) != want:
+        raise ValueError(f"logits (n,{','.join(map(str, want))},H,W) expected{' with margin=True' if margin else ''}, "
+                         f"got {tuple(shape)}")
+    if int(t) != t or int(step) != step or not 1 <= t <= 65535 or step < 1 or (k - 1) * step >= t:
+        raise ValueError(f"t = {t!r} frames (1 to 65535) and step = {step!r} (>= 1) must leave every one of the {k} "
+                         f"passes a frame")
+    need = 0
+    for j, c0 in enumerate(clip0):
+        if int(c0) != c0 or c0 < 0:
+            raise ValueError(f"clip0[{j}] = {c0!r}: the pass's first clip, an integer >= 0, expected")
+        need = max(need, c0 + n_clips(t - j * step))
+    if shape[0] < need:
+        raise ValueError(f"logits holds {shape[0]} clips, but the passes read {need} (clip0 {list(clip0)}, "
+                         f"{t} frames, step {step})")
+    return need
+
+
 def fuse_votes(labels, step, fuse_method="simple", force_generic=False):
     """Per-frame fusion of (K,T,H,W) uint8 pass labels -> (T-(step-1),H,W) uint8. ``force_generic``
-    runs SIMPLE on its generic kernel instead of the packed <= 16-vote one (A/B tests)."""
-    labels = labels.to(torch.uint8).contiguous()
+    runs SIMPLE on its generic kernel instead of the packed <= 16-vote one (A/B tests). ``labels``: on the
+    GPU (any integer dtype and strides: converted), K <= 64; ``step`` >= 1 with T - (step - 1) >= 1."""
+    _lib.on_gpu(labels, "labels")
+    check_fuse_votes_args(labels.shape, step)
     k, t, h, w = labels.shape
+    labels = labels.to(torch.uint8).contiguous()
     method = FUSE_METHODS.get(fuse_method.lower())
     if method is None:
         raise NotImplementedError(f"fuse_method {fuse_method!r}: supported {sorted(FUSE_METHODS)}")
@@ -195,7 +265,11 @@ def segment_a_video_with_fusion_device(video, model, interpolate_last=True, step
 
 
 def logit_margin(logits):
-    """(n,2,32,H,W) logits -> (n,32,H,W) margins l1 - l0 (what pass_labels(margin=True) consumes)."""
+    """(n,2,32,H,W) logits on the GPU (any dtype and strides: converted) -> (n,32,H,W) margins l1 - l0
+    (what pass_labels(margin=True) consumes)."""
+    _lib.on_gpu(logits, "logits")
+    if logits.dim() != 5 or logits.shape[1] != 2 or logits.shape[2] != CLIP:
+        raise ValueError(f"logits (n,2,{CLIP},H,W) expected, got {tuple(logits.shape)}")
     logits = logits.to(torch.float32).contiguous()
     n, _, c, h, w = logits.shape
     out = torch.empty((n, c, h, w), device=logits.device, dtype=torch.float32)
@@ -207,10 +281,12 @@ def logit_margin(logits):
 
 def pass_labels(logits, clip0, t, step, interpolate_last=True, margin=False):
     """(K,T,H,W) uint8 labels of the K shifted passes (softmax -> resample -> argmax). ``logits``
-    is (n,2,32,H,W), or (n,32,H,W) margins l1 - l0 with ``margin=True`` (bit-identical labels)."""
+    is (n,2,32,H,W), or (n,32,H,W) margins l1 - l0 with ``margin=True`` (bit-identical labels), on the GPU
+    (any dtype and strides: converted). Pass k reads clips [clip0[k], clip0[k] + n_clips(t - k * step)) of it:
+    ``logits`` must hold them all, else ValueError (the kernel takes K, clip0 and T on trust)."""
+    _lib.on_gpu(logits, "logits")
+    check_pass_labels_args(logits.shape, clip0, t, step, margin)
     k = len(clip0)
-    if k > MAX_PASSES:
-        raise ValueError(f"at most {MAX_PASSES} shifted passes are supported (got {k})")
     logits = logits.to(torch.float32).contiguous()
     h, w = logits.shape[-2:]
     labels = torch.empty((k, t, h, w), device=logits.device, dtype=torch.uint8)

@@ -140,7 +140,21 @@ class Engine:
         _lib.check(self.lib.clasfv_finalize(self.h), "clasfv_finalize")
 
     def forward(self, x, seg, mot, stream=None):
+        """x (n,3,t,h,w) -> seg (n,2,t,h,w) logits and mot (n,4,t,h,w), written into the caller's buffers:
+        all three contiguous float32 tensors on the engine's device, seg and mot overlapping neither each
+        other nor x (ValueError otherwise; nothing is converted, the library reads and writes their bytes)."""
+        for name, a in (("x", x), ("seg", seg), ("mot", mot)):
+            _lib.on_gpu(a, name, self.device, torch.float32)
+        if x.dim() != 5 or x.shape[1] != 3 or not x.is_contiguous():
+            raise ValueError(f"x: a contiguous (n,3,t,h,w) tensor expected, got {tuple(x.shape)} with strides {x.stride()}")
         n, c, t, hh, ww = x.shape
+        for name, a, ch in (("seg", seg, 2), ("mot", mot, 4)):
+            if tuple(a.shape) != (n, ch, t, hh, ww) or not a.is_contiguous():
+                raise ValueError(f"{name}: a contiguous {(n, ch, t, hh, ww)} tensor expected for x {tuple(x.shape)}, got "
+                                 f"{tuple(a.shape)} with strides {a.stride()}")
+        for (na, a), (nb, b) in ((("seg", seg), ("mot", mot)), (("seg", seg), ("x", x)), (("mot", mot), ("x", x))):
+            if _lib.overlap(a, b):
+                raise ValueError(f"{na} overlaps {nb}: the forward writes its outputs while it reads its input")
         _lib.check(self.lib.clasfv_forward(self.h, _lib.ptr(x), n, t, hh, ww, _lib.ptr(seg), _lib.ptr(mot),
                                            _lib.stream_ptr(stream, self.device)), "clasfv_forward")
 

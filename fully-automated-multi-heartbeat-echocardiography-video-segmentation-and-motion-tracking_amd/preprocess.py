@@ -16,9 +16,11 @@ from . import _lib
 
 
 def zeroone_normalize_(video):
-    """In place on a (3, ...) float32 contiguous device tensor; returns it."""
-    if video.shape[0] != 3 or video.dtype != torch.float32 or not video.is_contiguous():
-        raise ValueError("expected a contiguous float32 (3, ...) tensor")
+    """In place on a (3, ...) float32 contiguous device tensor; returns it. A host tensor is a ValueError
+    (zeroone_normalizer takes host data)."""
+    _lib.on_gpu(video, "video")
+    if video.dim() < 1 or video.shape[0] != 3 or video.dtype != torch.float32 or not video.is_contiguous():
+        raise ValueError("video: expected a contiguous float32 (3, ...) tensor")
     lib = _lib.load()
     # scratch for the per-block min/max partials, stream-ordered by the caching allocator
     ws = torch.empty(int(lib.clasfv_zeroone_workspace_bytes()) // 4, device=video.device, dtype=torch.float32)
@@ -29,9 +31,17 @@ def zeroone_normalize_(video):
 
 def zeroone_normalizer(image_data):
     """Drop-in for the reference function: numpy in -> numpy out (normalised in place, like the
-    reference's ``-=``/``/=``); a device tensor is normalised in place on the device."""
+    reference's ``-=``/``/=``); a device tensor is normalised in place on the device. A host tensor is host
+    data: it goes the numpy way through ``.numpy()`` (in place when it is float32, and returned; a new float32
+    tensor for any other dtype), never to the kernel as a host pointer."""
     if torch.is_tensor(image_data):
-        return zeroone_normalize_(image_data)
+        if image_data.is_cuda:
+            return zeroone_normalize_(image_data)
+        if image_data.dtype == torch.float32:
+            zeroone_normalizer(image_data.detach().numpy())
+            return image_data
+        # any other dtype (bfloat16 has no numpy form) is widened first, as the numpy branch widens arrays
+        return torch.from_numpy(zeroone_normalizer(image_data.detach().to(torch.float32).numpy()))
     arr = np.asarray(image_data)
     dev = torch.device("cuda", torch.cuda.current_device())
     t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(dev)

@@ -19,6 +19,13 @@ from . import _lib
 
 
 def _check(img, motion):
+    """Refuses what the library would misread (it takes raw float32 device pointers): a host tensor, another
+    dtype (never converted: a float64 image or the bf16 motion of an autocast region is the caller's to cast),
+    two devices. Only strides are converted."""
+    _lib.on_gpu(img, "img", dtype=torch.float32)
+    _lib.on_gpu(motion, "motion", dtype=torch.float32)
+    if motion.device != img.device:
+        raise ValueError(f"img and motion must be on one GPU, not on {img.device} and {motion.device}")
     if img.dim() != 4 or motion.dim() != 4 or motion.shape[1] != 2:
         raise ValueError("img (N,C,H,W) and motion (N,2,H,W) expected")
     n, c, h, w = img.shape
@@ -34,9 +41,15 @@ def _warp_forward(img, motion, out=None):
     n, c, h, w = img.shape
     if out is None:
         out = torch.empty_like(img)
-    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.shape != img.shape or out.device != img.device
-          or not out.is_contiguous()):
-        raise ValueError(f"out= must be a contiguous float32 tensor of img's shape {tuple(img.shape)} on {img.device}")
+    else:
+        if not torch.is_tensor(out):
+            raise TypeError(f"out= must be a torch tensor on {img.device}, not {type(out).__name__}")
+        if (out.dtype != torch.float32 or out.shape != img.shape or out.device != img.device
+                or not out.is_contiguous()):
+            raise ValueError(f"out= must be a contiguous float32 tensor of img's shape {tuple(img.shape)} on {img.device}")
+        for name, t in (("img", img), ("motion", motion)):  # every block reads both while others write out
+            if _lib.overlap(out, t):
+                raise ValueError(f"out= overlaps {name}: the warp cannot run in place")
     lib = _lib.load()
     _lib.check(lib.clasfv_warp(_lib.ptr(img), n, c, h, w, _lib.ptr(motion), motion.stride(0), motion.stride(1),
                                _lib.ptr(out), _lib.stream_ptr(device=img.device)), "clasfv_warp")
@@ -74,7 +87,12 @@ def warp(img, motion, out=None):
     """img (N,C,H,W) float32 on the device, motion (N,2,H,W) (any strides on N and the channel
     dim; H,W contiguous) -> warped (N,C,H,W) = grid_sample(img, generate_2dmotion_field(img, motion),
     bilinear, border, align_corners=False). Differentiable in img and motion. ``out`` (no autograd): a
-    contiguous float32 tensor of img's shape on img's device to write into, else ValueError."""
+    contiguous float32 tensor of img's shape on img's device to write into, overlapping neither img nor
+    motion, else ValueError. img and motion must be float32 tensors on one GPU (ValueError; nothing is
+    converted but strides); they may overlap each other."""
+    for name, t in (("img", img), ("motion", motion)) + ((("out", out),) if out is not None else ()):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a torch tensor on the GPU, not {type(t).__name__}")
     if torch.is_grad_enabled() and (img.requires_grad or motion.requires_grad):
         if out is not None:
             raise ValueError("out= is not supported under autograd")

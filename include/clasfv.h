@@ -343,7 +343,10 @@ int clasfv_fuse_votes(const uint8_t* labels_dev, int K, int T, int step, int H, 
 /* out (N,C,H,W) = bilinear sample of img at (linspace_W[j] + motion[n,0,i,j],
  * linspace_H[i] + motion[n,1,i,j]), border padding, align_corners=False. motion is (N,2,H,W) with
  * arbitrary element strides for n and the channel (so a slice motion[:, 0:2, t] of (N,4,T,H,W) can
- * be passed directly): element (n,c,i,j) at motion_dev[n*m_sn + c*m_sc + i*W + j]. */
+ * be passed directly): element (n,c,i,j) at motion_dev[n*m_sn + c*m_sc + i*W + j]. img_dev and motion_dev
+ * may overlap each other; out_dev must overlap neither. CLASFV_EINVAL, before any HIP call, for a null
+ * pointer, N, C, H or W < 1, or out overlapping img or motion (the bytes from the first to the last
+ * element the strides reach). */
 int clasfv_warp(const float* img_dev, int N, int C, int H, int W, const float* motion_dev, int64_t m_sn,
                 int64_t m_sc, float* out_dev, void* stream);
 
@@ -351,7 +354,9 @@ int clasfv_warp(const float* img_dev, int N, int C, int H, int W, const float* m
  * grad_img_dev (N,C,H,W) += d loss / d img (atomically accumulated: zero it first; may be NULL),
  * grad_motion_dev (N,2,H,W) dense = d loss / d motion (may be NULL), from grad_out_dev (N,C,H,W).
  * grad_motion is bit-exact vs PyTorch's CPU grid_sample backward; grad_img matches it to float
- * rounding (different summation order). motion strides as in clasfv_warp. */
+ * rounding (different summation order). motion strides as in clasfv_warp. The inputs may overlap each
+ * other; CLASFV_EINVAL, before any HIP call, for grad_img or grad_motion overlapping an input or each
+ * other. */
 int clasfv_warp_backward(const float* grad_out_dev, const float* img_dev, int N, int C, int H, int W,
                          const float* motion_dev, int64_t m_sn, int64_t m_sc, float* grad_img_dev,
                          float* grad_motion_dev, void* stream);

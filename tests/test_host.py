@@ -32,6 +32,172 @@ def test_library_builds_and_exports_every_header_symbol():
     assert set(funcs) == set(_lib.SIGNATURES), "ctypes signatures out of sync with include/clasfv.h"
 
 
+# ---- the binding's types against the header's ---------------------------------------------------------------
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
+            "int32_t": ctypes.c_int32, "uint8_t": ctypes.c_uint8}
+
+
+def _pointees():
+    from clasfv_amd import _lib
+    return dict(_SCALARS, clasfv_plan_launch_t=_lib.PlanLaunch, clasfv_plan_buffer_t=_lib.PlanBuffer,
+                clasfv_plan_range_t=_lib.PlanRange, clasfv_t=ctypes.c_void_p)
+
+
+def header_text():
+    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+
+
+def c_type_to_ctypes(ctype):
+    """The ctypes types a C parameter or return type of the header may be bound as: exactly one for int,
+    int64_t, double and const char*; a typed pointer or c_void_p for every other pointer."""
+    t = " ".join(ctype.replace("*", " * ").split())
+    stars = t.count("*")
+    base = t.replace("*", "").replace("const", "").split()
+    assert len(base) == 1, f"cannot parse the C type {ctype!r}"
+    base = base[0]
+    if base == "char" and "const" in t and stars >= 1:   # const char* is a string, const char** a pointer to one
+        return {ctypes.c_char_p} if stars == 1 else {ctypes.POINTER(ctypes.c_char_p)}
+    if base == "clasfv_t":                               # an opaque handle: itself a pointer
+        return {ctypes.c_void_p} if stars == 0 else {ctypes.POINTER(ctypes.c_void_p)}
+    if stars == 0:
+        return {_SCALARS[base]}
+    if base == "void":
+        return {ctypes.c_void_p} if stars == 1 else {ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)}
+    assert stars == 1, ctype
+    return {ctypes.c_void_p, ctypes.POINTER(_pointees()[base])}
+
+
+def header_prototypes():
+    """{name: (return C type, [parameter C types])} of every clasfv_ function the header declares."""
+    out = {}
+    for ret, name, params in re.findall(r"^\s*(const char\s*\*|int64_t|int|void)\s*(clasfv_\w+)\s*\(([^)]*)\)\s*;",
+                                        header_text(), re.M):
+        types = []
+        for p in [q.strip() for q in params.split(",")]:
+            if p == "void":
+                continue
+            m = re.fullmatch(r"(.*?)(\w+)\s*(\[\w*\])?", p, re.S)
+            assert m, p
+            types.append(m.group(1).strip() + ("*" if m.group(3) else ""))   # an array parameter is a pointer
+        out[name] = (ret, types)
+    return out
+
+
+def signature_problems(signatures):
+    """Every place where ``signatures`` (name -> (restype, argtypes)) is not what the header declares."""
+    protos, bad = header_prototypes(), []
+    for name, (ret, params) in sorted(protos.items()):
+        if name not in signatures:
+            bad.append(f"{name}: not bound")
+            continue
+        res, args = signatures[name]
+        if res not in c_type_to_ctypes(ret):
+            bad.append(f"{name}: returns {ret}, bound as {res.__name__}")
+        if len(args) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, {len(args)} bound")
+            continue
+        for i, (c, a) in enumerate(zip(params, args)):
+            if a not in c_type_to_ctypes(c):
+                bad.append(f"{name}: parameter {i} is {c}, bound as {a.__name__}")
+    return bad
+
+
+def test_signature_types_match_the_header():
+    """Every prototype of include/clasfv.h parsed into C types and held against _lib.SIGNATURES, restype
+    included: an int64_t stride bound as c_int passes a name comparison and drops the stride's high bits. A
+    seeded mismatch (clasfv_warp's m_sn as c_int, a wrong restype) is reported, and nothing else is."""
+    from clasfv_amd import _lib
+    protos = header_prototypes()
+    assert set(protos) == set(header_functions()) == set(_lib.SIGNATURES)
+    assert protos["clasfv_warp"] == ("int", ["const float*", "int", "int", "int", "int", "const float*", "int64_t",
+                                             "int64_t", "float*", "void*"])
+    assert protos["clasfv_param_info"][1][-1] == "int64_t*" and protos["clasfv_last_error"][1] == []
+    assert signature_problems(_lib.SIGNATURES) == []
+    seeded = dict(_lib.SIGNATURES)
+    res, args = seeded["clasfv_warp"]
+    seeded["clasfv_warp"] = (res, args[:6] + [ctypes.c_int] + args[7:])
+    seeded["clasfv_workspace_bytes"] = (ctypes.c_int, seeded["clasfv_workspace_bytes"][1])
+    assert signature_problems(seeded) == ["clasfv_warp: parameter 6 is int64_t, bound as c_int",
+                                          "clasfv_workspace_bytes: returns int64_t, bound as c_int"]
+
+
+_PLAN_STRUCTS = {"clasfv_plan_range_t": "PlanRange", "clasfv_plan_launch_t": "PlanLaunch",
+                 "clasfv_plan_buffer_t": "PlanBuffer"}
+
+
+def header_struct_fields():
+    """{typedef name: [field names in order]} of the header's three plan structs."""
+    out = {}
+    for body, name in re.findall(r"typedef struct \w+\s*\{(.*?)\}\s*(\w+)\s*;", header_text(), re.S):
+        fields = []
+        for decl in [d.strip() for d in body.split(";") if d.strip()]:
+            names = decl.split(",")
+            names[0] = names[0].split()[-1]   # drop the type of the first declarator
+            fields += [re.sub(r"\[.*\]|\*", "", n).strip() for n in names]
+        out[name] = fields
+    return out
+
+
+def layout_problems(layout, structs):
+    """``layout``: the lines "type sizeof" / "type.field offset size" a C compiler printed; against ctypes."""
+    want = {}
+    for line in layout.split("\n"):
+        if line.strip():
+            key, *nums = line.split()
+            want[key] = tuple(int(v) for v in nums)
+    bad = []
+    for cname, fields in header_struct_fields().items():
+        st = structs[cname]
+        if ctypes.sizeof(st) != want[cname][0]:
+            bad.append(f"{cname}: {want[cname][0]} bytes, {st.__name__} has {ctypes.sizeof(st)}")
+        if [f[0] for f in st._fields_] != fields:
+            bad.append(f"{cname}: fields {fields}, {st.__name__} has {[f[0] for f in st._fields_]}")
+            continue
+        for f in fields:
+            d = getattr(st, f)
+            if (d.offset, d.size) != want[f"{cname}.{f}"]:
+                bad.append(f"{cname}.{f}: offset, size {want[f'{cname}.{f}']}, {st.__name__} has {(d.offset, d.size)}")
+    return bad
+
+
+def test_plan_struct_layouts_match_the_header(tmp_path):
+    """sizeof and every offsetof of the three plan structs, printed by a C program that includes the header
+    and is compiled with the host compiler, against ctypes.sizeof and the field offsets of PlanRange,
+    PlanLaunch and PlanBuffer. A seeded mismatch (two fields of PlanBuffer swapped) is reported."""
+    import shutil
+    import subprocess
+    from clasfv_amd import _lib
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")   # the clang that builds the library compiles C for the host too
+    cc = next((p for p in [shutil.which(c) for c in ("cc", "gcc", "clang")] +
+               [os.path.join(rocm, "llvm", "bin", "clang"), os.path.join(rocm, "lib", "llvm", "bin", "clang")]
+               if p and os.path.exists(p)), None)
+    assert cc is not None, "no C compiler for the host: neither cc, gcc nor clang on PATH, nor ROCm's clang"
+    fields = header_struct_fields()
+    assert set(fields) == set(_PLAN_STRUCTS) and fields["clasfv_plan_range_t"][-2:] == ["offset", "bytes"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "clasfv.h"', 'int main(void) {']
+    for cname, names in fields.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'  printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f in names]
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], check=True)
+    layout = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
+    structs = {c: getattr(_lib, p) for c, p in _PLAN_STRUCTS.items()}
+    assert layout_problems(layout, structs) == []
+
+    class Swapped(ctypes.Structure):   # offset and bytes in each other's place: same size, same types
+        _fields_ = [f for f in _lib.PlanBuffer._fields_[:5]] + [_lib.PlanBuffer._fields_[6], _lib.PlanBuffer._fields_[5],
+                                                                 _lib.PlanBuffer._fields_[7]]
+    problems = layout_problems(layout, dict(structs, clasfv_plan_buffer_t=Swapped))
+    assert len(problems) == 1 and problems[0].startswith("clasfv_plan_buffer_t: fields")
+
+    class Narrow(ctypes.Structure):    # the same names in order, one field of another width
+        _fields_ = [(n, ctypes.c_int32 if n == "total" else t) for n, t in _lib.PlanBuffer._fields_]
+    problems = layout_problems(layout, dict(structs, clasfv_plan_buffer_t=Narrow))
+    assert problems and all(p.startswith("clasfv_plan_buffer_t") for p in problems)
+
+
 def test_abi_version_matches_header():
     from clasfv_amd import _lib
     m = re.search(r"#define CLASFV_ABI_VERSION (\d+)", open(HEADER).read())

@@ -285,6 +285,58 @@ def test_track_refuses_bad_arguments():
     assert call_track(ok["img"], n, c, h, w, ok["mot"], True, t, 0, 1, 3, NEAREST | FORCE_STEPS, ok["out"]) == 0
 
 
+def test_warp_refuses_an_output_that_overlaps_an_input():
+    """clasfv_warp and clasfv_warp_backward on real tensors: an output over img, over motion (between the
+    planes of a strided slice included) or over grad_out is CLASFV_EINVAL with a message and nothing is written;
+    outputs that only touch an input's end run, and write what separate buffers give."""
+    from clasfv_amd import _lib
+    n, c, h, w, t = 2, 2, 5, 9, 3
+    plane, numel = h * w, n * c * h * w
+    g = torch.Generator().manual_seed(11)
+    buf = Guarded(3 * numel)                       # img, then out, then a spare, adjacent
+    img_v = torch.randn(numel, generator=g).to(dev())
+    buf.t[:numel] = img_v
+    img, adjacent = buf.t[:numel], buf.t[numel:2 * numel]
+    field = torch.tanh(torch.randn(n, 4, t, h, w, generator=g) * 0.4).to(dev())
+    mot = field[:, 2:, 1]
+    stream = _lib.stream_ptr(None, dev())
+
+    def warp(out_p, img_p=ptr(img)):
+        return lib().clasfv_warp(img_p, n, c, h, w, ptr(mot), mot.stride(0), mot.stride(1), out_p, stream)
+
+    before = buf.raw.clone()
+    field_before = field.clone()
+    inside = field.view(-1)[(2 * t + 2) * plane:]   # between the slice's two planes of clip 0
+    for out_p in (ptr(img), ptr(buf.t[1:]), ptr(buf.t[numel - 1:]), ptr(mot), ptr(inside), ptr(field.view(-1)[4 * plane:])):   # the last: out's end reaches the slice
+        assert warp(out_p) == EINVAL
+        assert b"out overlaps" in lib().clasfv_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(buf.raw, before) and torch.equal(field, field_before)
+    assert warp(ptr(adjacent)) == 0                # out starts where img ends
+    want = torch.empty(numel, device=dev())
+    assert warp(ptr(want)) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(adjacent, want) and torch.equal(buf.t[:numel], img_v) and buf.guards_intact()
+    assert bool((buf.raw[buf.lo + 2 * numel:buf.hi] == -1).all())
+
+    gout = torch.randn(numel, generator=g).to(dev())
+    gi, gm = torch.zeros(numel, device=dev()), torch.full((n * 2 * plane,), float("nan"), device=dev())
+
+    def backward(gi_p, gm_p):
+        return lib().clasfv_warp_backward(ptr(gout), ptr(img), n, c, h, w, ptr(mot), mot.stride(0), mot.stride(1), gi_p,
+                                          gm_p, stream)
+
+    for gi_p, gm_p in ((ptr(img), ptr(gm)), (ptr(gout), ptr(gm)), (ptr(gi), ptr(mot)), (ptr(gi), ptr(gout[numel - 1:])),
+                       (ptr(gi), ptr(gi)), (NUL, ptr(inside)), (ptr(field.view(-1)[4 * plane:]), NUL)):
+        assert backward(gi_p, gm_p) == EINVAL
+        assert b"overlaps" in lib().clasfv_last_error()
+    torch.cuda.synchronize()
+    assert not bool(gi.any()) and bool(torch.isnan(gm).all()) and torch.equal(field, field_before)
+    assert backward(ptr(gi), ptr(gm)) == 0
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(gm).any())
+
+
 # ---- warp.track under autograd -------------------------------------------------------------------------
 GRAD_RTOL, GRAD_ATOL = 1e-4, 1e-7   # the project's bars for chained-warp gradients (tests/test_gpu.py)
 # Largest deviation allowed, in units of that bar (max |got - want| / (atol + rtol |want|)), per direction.

@@ -40,6 +40,50 @@ def test_track_refusals_need_no_gpu():
         assert lib.clasfv_track(*[a[k] for k in order]) == EBADSHAPE, change
 
 
+def test_warp_overlap_refusals_need_no_gpu():
+    """clasfv_warp refuses an out that overlaps img or motion, clasfv_warp_backward a gradient that overlaps
+    an input or the other gradient: CLASFV_EINVAL with a message, before any HIP call (the pointers here are
+    never dereferenced). motion's range runs from its first to its last element under the strides given, so
+    an out between the planes of a strided slice is refused. These pointers are made up, and a call that passed
+    the checks would launch on them, so the test runs only where no GPU is visible; where there is one, the
+    same refusals and the calls that pass, adjacent buffers among them, run on real tensors in
+    tests/test_track_gpu.py."""
+    import torch
+    from clasfv_amd import _lib
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is visible: made-up pointers are handed to the library only where nothing can launch")
+    lib = _lib.load()
+    P = ctypes.c_void_p
+    n, c, h, w = 2, 2, 5, 9
+    img_b, hw = n * c * h * w * 4, h * w * 4
+    IMG, MOT, OUT, G1, G2 = 0x100000, 0x200000, 0x300000, 0x400000, 0x500000
+    sn, sc = 12 * h * w, 3 * h * w     # the slice [:, 2:, t] of a (n,4,3,h,w) field: it spans 16 planes
+    span = 16 * hw
+
+    def warp(out, img=IMG, mot=MOT, m_sn=sn, m_sc=sc):
+        return lib.clasfv_warp(P(img), n, c, h, w, P(mot), m_sn, m_sc, P(out), None)
+
+    for out, why in ((IMG, "img"), (IMG + img_b - 4, "img"), (IMG - img_b + 4, "img"), (MOT, "motion"),
+                     (MOT + span - 4, "motion"), (MOT - img_b + 4, "motion"), (MOT + 4 * hw, "motion")):
+        assert warp(out) == EINVAL, hex(out)
+        assert f"out overlaps {why}".encode() in lib.clasfv_last_error(), hex(out)
+    assert warp(MOT + 2 * hw, m_sn=2 * h * w, m_sc=-h * w) == EINVAL        # a negative channel stride reaches back
+    assert warp(MOT - img_b - hw + 4, m_sn=2 * h * w, m_sc=-h * w) == EINVAL
+
+    def backward(gimg=G1, gmot=G2, gout=OUT):
+        return lib.clasfv_warp_backward(P(gout), P(IMG), n, c, h, w, P(MOT), sn, sc, P(gimg) if gimg else None,
+                                        P(gmot) if gmot else None, None)
+
+    for kw, msg in ((dict(gimg=IMG), "grad_img overlaps an input"), (dict(gimg=OUT + 4), "grad_img overlaps an input"),
+                    (dict(gimg=MOT + span - 4), "grad_img overlaps an input"),
+                    (dict(gmot=IMG + img_b - 4), "grad_motion overlaps an input"),
+                    (dict(gmot=MOT), "grad_motion overlaps an input"), (dict(gimg=None, gmot=OUT), "grad_motion overlaps"),
+                    (dict(gimg=G1, gmot=G1 + img_b - 4), "grad_img overlaps grad_motion")):
+        assert backward(**kw) == EINVAL, kw
+        assert msg.encode() in lib.clasfv_last_error(), kw
+    assert backward(gimg=None, gmot=None) == EINVAL
+
+
 def test_track_constants_match_header():
     from clasfv_amd import _lib
     defs = {k: int(v, 0) for k, v in re.findall(r"#define CLASFV_TRACK_(\w+)\s+(\w+)", open(HEADER).read())}
