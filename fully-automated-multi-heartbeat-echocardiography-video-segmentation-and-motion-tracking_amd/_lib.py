@@ -3,6 +3,7 @@
 There is no CPU fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
 import ctypes
+import numbers
 import os
 
 from .build import LIB_PATH
@@ -96,6 +97,28 @@ SIGNATURES = {
 ABI_VERSION = 3  # CLASFV_ABI_VERSION of include/clasfv.h these signatures describe
 FUSE_MAJORITY, FUSE_SIMPLE, FUSE_STAPLE, FUSE_ITKVOTING = 0, 1, 2, 3
 FUSE_FORCE_GENERIC = 0x100
+# CLASFV_FUSE_CLEAN, CLASFV_FUSE_CLEAN_HOLES(n), CLASFV_CLEAN_* (include/clasfv.h)
+FUSE_CLEAN = 0x200
+CLEAN_DEFAULT_HOLES, CLEAN_MAX_HOLES, CLEAN_MAX_PIXELS = 128, 32767, 53248
+
+
+def fuse_clean_holes(n):
+    """CLASFV_FUSE_CLEAN_HOLES(n): the hole threshold in bits 16..30 of a clasfv_fuse_votes method."""
+    return n << 16
+
+
+def clean_bits(holesize, name="holesize"):
+    """CLASFV_FUSE_CLEAN with its hole threshold, for OR-ing into a method; ValueError unless ``holesize`` is
+    an integer in 1..32767. Host arithmetic."""
+    if isinstance(holesize, bool) or not isinstance(holesize, numbers.Integral) or not 1 <= holesize <= CLEAN_MAX_HOLES:
+        raise ValueError(f"{name} {holesize!r} must be an integer in 1..{CLEAN_MAX_HOLES}")
+    return FUSE_CLEAN | fuse_clean_holes(int(holesize))
+
+
+def check_clean_frame(h, w, name):
+    """ValueError for a frame the cleanup kernel cannot hold (CLASFV_CLEAN_MAX_PIXELS)."""
+    if h * w > CLEAN_MAX_PIXELS:
+        raise ValueError(f"{name}: cleanup takes frames of at most {CLEAN_MAX_PIXELS} pixels, got {h} x {w}")
 # CLASFV_TRACK_* (include/clasfv.h)
 TRACK_BILINEAR, TRACK_NEAREST = 0, 1
 TRACK_FORCE_STEPS, TRACK_FORCE_LDS = 0x100, 0x200

@@ -19,8 +19,9 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(REPO_DIR, "include")
 LIB_PATH = os.path.join(PKG_DIR, "libclasfv.so")
 SOURCES = ["engine.hip", "conv.hip", "conv_patch.hip", "winograd.hip", "winograd2.hip", "winograd4.hip", "winograd4w.hip",
-           "winograd_t.hip", "decoder.hip", "plumbing.hip", "twalk.hip", "track.hip", "lvgeom.hip", "render.hip"]
-HEADERS = ["common.h", "lvgeom.h", "plumbing.h", "render.h", "track.h", "warp_math.h", "wino4_common.h"]
+           "winograd_t.hip", "decoder.hip", "plumbing.hip", "twalk.hip", "track.hip", "lvgeom.hip", "render.hip",
+           "cleanup.hip"]
+HEADERS = ["cleanup.h", "common.h", "lvgeom.h", "plumbing.h", "render.h", "track.h", "warp_math.h", "wino4_common.h"]
 ARCH = os.environ.get("CLASFV_OFFLOAD_ARCH", "gfx950")
 # Per-file extra flags. winograd_t.hip: no SLP vectorisation -- packed f32 VALU (v_pk_*) beside
 # MFMAs costs issue cycles and the pack/unpack moves doubled the temporal kernel's vector stream.

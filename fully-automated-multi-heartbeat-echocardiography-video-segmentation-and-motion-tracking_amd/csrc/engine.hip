@@ -20,6 +20,7 @@
 
 #include "clasfv.h"
 #include "common.h"
+#include "cleanup.h"
 #include "lvgeom.h"
 #include "plumbing.h"
 #include "render.h"
@@ -1922,7 +1923,14 @@ int clasfv_fuse_votes(const uint8_t* labels, int K, int T, int step, int H, int 
                       void* stream) {
   if (!labels || !fused || K < 1 || K > CLASFV_MAX_PASSES || T < 1 || step < 1 || T - (step - 1) < 1)
     return fail(CLASFV_EINVAL, "bad argument (K must be in [1, 64])");
-  const int m = method & ~CLASFV_FUSE_FORCE_GENERIC;
+  // CLASFV_FUSE_CLEAN and its hole threshold (bits 16..30) ride on the method; bit 31 belongs to nobody
+  const unsigned bits = (unsigned)method;
+  const bool clean = (bits & CLASFV_FUSE_CLEAN) != 0;
+  const int holes = (int)((bits >> 16) & 0x7FFFu);
+  if ((bits >> 31) || (holes && !clean))
+    return fail(CLASFV_EINVAL, "unknown method (hole threshold without CLASFV_FUSE_CLEAN, or bit 31)");
+  const int fuse = (int)(bits & 0xFFFFu & ~(unsigned)CLASFV_FUSE_CLEAN);  // what launch_fuse_votes takes
+  const int m = fuse & ~CLASFV_FUSE_FORCE_GENERIC;
   if (m != CLASFV_FUSE_MAJORITY && m != CLASFV_FUSE_SIMPLE && m != CLASFV_FUSE_STAPLE && m != CLASFV_FUSE_ITKVOTING)
     return fail(CLASFV_EINVAL, "unknown method");
   if (H < 1 || W < 1) return fail(CLASFV_EINVAL, "bad argument (H and W must be >= 1)");
@@ -1930,7 +1938,12 @@ int clasfv_fuse_votes(const uint8_t* labels, int K, int T, int step, int H, int 
     return fail(CLASFV_EINVAL, "bad argument (majority / ITK voting take at most 65535 output frames)");
   if (m == CLASFV_FUSE_SIMPLE && (int64_t)H * W > CLASFV_SIMPLE_MAX_HW)
     return fail(CLASFV_EBADSHAPE, "SIMPLE keeps one frame's estimate in LDS: H * W must be <= 162816");
-  HIP_TRY(launch_fuse_votes(labels, K, T, step, H * W, method, fused, (hipStream_t)stream));
+  if (clean && (int64_t)H * W > CLASFV_CLEAN_MAX_PIXELS)
+    return fail(CLASFV_EBADSHAPE, "CLASFV_FUSE_CLEAN keeps one frame's labels in LDS: H * W must be <= 53248");
+  HIP_TRY(launch_fuse_votes(labels, K, T, step, H * W, fuse, fused, (hipStream_t)stream));
+  if (clean)
+    HIP_TRY(launch_cleanup_frames(fused, (int64_t)(T - (step - 1)), H, W, holes ? holes : CLASFV_CLEAN_DEFAULT_HOLES,
+                                  (hipStream_t)stream));
   return CLASFV_OK;
 }
 

@@ -160,7 +160,7 @@ def exchange_stats(lengths, num_clips, step, world, h=112, w=112, interpolate_la
 
 def segment_videos_sharded(videos_dev, model, num_clips=5, step=1, fuse_method="simple", interpolate_last=True,
                            rank=0, world=1, batch_size=None, clip_fn=None, lengths=None, force_exchange=False,
-                           exchange_events=None):
+                           exchange_events=None, cleanup=False, holesize=128):
     """Fuse a batch of device videos (each (3,T,H,W)) with clips sharded over ranks.
 
     Returns {video index: fused (T',H,W) uint8 device tensor} for the videos this rank owns
@@ -169,7 +169,11 @@ def segment_videos_sharded(videos_dev, model, num_clips=5, step=1, fuse_method="
     (``videos_needed``). ``force_exchange``: ship logit margins through the all_to_all even when no
     clip crosses ranks (tests; the result is the same). ``exchange_events``: a list that receives one
     (start, end) pair of timing events on the current stream around the margin computation and the
-    all_to_all, when the exchange runs (bench.py reports their elapsed time)."""
+    all_to_all, when the exchange runs (bench.py reports their elapsed time). ``cleanup``, ``holesize``: the
+    owning rank cleans every fused frame in the fusion call (fuse_utils.fuse_votes)."""
+    if cleanup:
+        from . import _lib
+        _lib.clean_bits(holesize)  # refused before any device work
     if lengths is None:
         lengths = [v.shape[1] for v in videos_dev]
     plans, n_total = global_clip_plan(list(lengths), num_clips, step, interpolate_last)
@@ -214,5 +218,5 @@ def segment_videos_sharded(videos_dev, model, num_clips=5, step=1, fuse_method="
         lg = mine[at: at + p["n"]]
         at += p["n"]
         labels = FU.pass_labels(lg, p["clip0"], p["T"], step, interpolate_last, margin=margin)
-        out[vi] = FU.fuse_votes(labels, step, fuse_method)
+        out[vi] = FU.fuse_votes(labels, step, fuse_method, cleanup=cleanup, holesize=holesize)
     return out

@@ -192,6 +192,37 @@ def lv_curve(masks, label=1, spacing=(1.0, 1.0)):
     return LvCurve(area, geom)
 
 
+def cleanup_masks(masks, label=1, holesize=128):
+    """cleanupBinary of the reference (src/utils/camus_validate.py:284-352) for every frame, on the device, in
+    one call: the 8-connected component of ``masks == label`` with the largest filled area is kept and its
+    holes of fewer than ``holesize`` pixels (an integer in 1..32767) are filled; include/clasfv.h states the
+    rule (clasfv_fuse_votes, CLASFV_FUSE_CLEAN). ``masks``: a device tensor (T,H,W) or (H,W) of an integer
+    dtype, frames of at most 53248 pixels. Returns uint8 0/1 of the same shape on the masks' stream."""
+    import torch
+    from . import _lib
+    if not torch.is_tensor(masks):
+        raise ValueError("masks must be a tensor on the GPU (the library reads its device pointer)")
+    if masks.is_floating_point() or masks.is_complex():
+        raise ValueError(f"masks of an integer dtype expected, not {masks.dtype}")
+    if masks.dim() not in (2, 3) or masks.numel() == 0:
+        raise ValueError(f"masks (T,H,W) or (H,W) with at least one frame expected, got {tuple(masks.shape)}")
+    h, w = masks.shape[-2:]
+    _lib.check_clean_frame(h, w, "masks")
+    method = _lib.FUSE_MAJORITY | _lib.clean_bits(holesize)
+    if not masks.is_cuda:
+        raise ValueError(f"masks must be on the GPU (the library reads their device pointer), not on {masks.device}")
+    frames = (masks == label).to(torch.uint8).contiguous()  # K = 1: one pass's votes
+    out = torch.empty_like(frames)
+    t = frames.numel() // (h * w)
+    lib = _lib.load()
+    for at in range(0, t, 65535):  # majority takes at most 65535 output frames per call
+        n = min(65535, t - at)
+        src, dst = frames.view(-1, h, w)[at:at + n], out.view(-1, h, w)[at:at + n]
+        _lib.check(lib.clasfv_fuse_votes(_lib.ptr(src), 1, n, 1, h, w, method, _lib.ptr(dst),
+                                         _lib.stream_ptr(device=masks.device)), "clasfv_fuse_votes")
+    return out
+
+
 def ef_from_curve(area, volume, name, return_edes=False):
     """compute_ef_using_putative_clips from a per-frame curve (LvCurve.area, LvCurve.volume of one video;
     arrays or tensors): the same ED / ES pairs, EF = (V[ED] - V[ES]) / V[ED] * 100, negative EFs reported

@@ -19,6 +19,9 @@ itk::LabelVotingImageFilter with its default undecided label: ties -> 2), ``simp
 Langerak 2010) and ``staple`` (STAPLE, Warfield 2004), up to 64 passes. LabelFusion itself is not
 available, so every rule but ``majority`` (pinned by the reference-run goldens of its stub) is
 parity-unpinned.
+``cleanup=True`` (with ``holesize``) on ``fuse_votes`` and the two segment functions cleans every fused frame in
+the fusion call: the reference's cleanupBinary (src/utils/camus_validate.py:284-352) on the device
+(CLASFV_FUSE_CLEAN, include/clasfv.h), parity-unpinned as well.
 """
 import numpy as np
 import torch
@@ -218,19 +221,27 @@ def check_pass_labels_args(shape, clip0, t, step, margin=False):
     return need
 
 
-def fuse_votes(labels, step, fuse_method="simple", force_generic=False):
+def fuse_votes(labels, step, fuse_method="simple", force_generic=False, cleanup=False, holesize=128):
     """Per-frame fusion of (K,T,H,W) uint8 pass labels -> (T-(step-1),H,W) uint8. ``force_generic``
     runs SIMPLE on its generic kernel instead of the packed <= 16-vote one (A/B tests). ``labels``: on the
-    GPU (any integer dtype and strides: converted), K <= 64; ``step`` >= 1 with T - (step - 1) >= 1."""
+    GPU (any integer dtype and strides: converted), K <= 64; ``step`` >= 1 with T - (step - 1) >= 1.
+    ``cleanup=True`` cleans every fused frame in the same call (CLASFV_FUSE_CLEAN, include/clasfv.h: the label-1
+    component of largest filled area is kept and its holes below ``holesize`` pixels, an integer in 1..32767,
+    are filled); frames of at most 53248 pixels."""
     _lib.on_gpu(labels, "labels")
     check_fuse_votes_args(labels.shape, step)
     k, t, h, w = labels.shape
+    clean = 0
+    if cleanup:
+        clean = _lib.clean_bits(holesize)
+        _lib.check_clean_frame(h, w, "labels")
     labels = labels.to(torch.uint8).contiguous()
     method = FUSE_METHODS.get(fuse_method.lower())
     if method is None:
         raise NotImplementedError(f"fuse_method {fuse_method!r}: supported {sorted(FUSE_METHODS)}")
     if force_generic:
         method |= _lib.FUSE_FORCE_GENERIC
+    method |= clean
     fused = torch.empty((t - (step - 1), h, w), device=labels.device, dtype=torch.uint8)
     lib = _lib.load()
     _lib.check(lib.clasfv_fuse_votes(_lib.ptr(labels), k, t, step, h, w, method, _lib.ptr(fused),
@@ -246,10 +257,13 @@ def ctypes_int32_array(vals):
 
 
 def segment_a_video_with_fusion_device(video, model, interpolate_last=True, step=1, num_clips=10, fuse_method="simple",
-                                       class_list=(0, 1), batch_size=None, strict_reference=True):
+                                       class_list=(0, 1), batch_size=None, strict_reference=True, cleanup=False,
+                                       holesize=128):
     """Same as segment_a_video_with_fusion but returns the fused (T',H,W) uint8 mask on the device."""
     if list(class_list) != [0, 1]:
         raise ValueError("the engine fuses the two CLAS-FV classes [0, 1]")
+    if cleanup:
+        _lib.clean_bits(holesize)  # refused before any device work
     dev = _device_of(model)
     v = to_device_video(video, dev)
     t = v.shape[1]
@@ -260,8 +274,14 @@ def segment_a_video_with_fusion_device(video, model, interpolate_last=True, step
     clips = build_clips(v, table, interpolate_last)
     logits = run_model(model, clips, batch_size)
     labels = pass_labels(logits, clip0, t, step, interpolate_last)
-    fused = fuse_votes(labels, step, fuse_method)
-    return fused if strict_reference else keep_dropped_frames(labels, fused, step)
+    fused = fuse_votes(labels, step, fuse_method, cleanup=cleanup, holesize=holesize)
+    if strict_reference:
+        return fused
+    if not cleanup or step == 1:
+        return keep_dropped_frames(labels, fused, step)
+    # pass 0's frames 1..step-1, re-inserted with their single vote, are cleaned like the fused ones
+    kept = fuse_votes(labels[:1, 1:step], 1, "majority", cleanup=True, holesize=holesize)
+    return torch.cat([fused[:1], kept, fused[1:]])
 
 
 def logit_margin(logits):
@@ -300,9 +320,10 @@ def pass_labels(logits, clip0, t, step, interpolate_last=True, margin=False):
 
 
 def segment_a_video_with_fusion(video, model, interpolate_last=True, step=1, num_clips=10, fuse_method="simple",
-                                class_list=[0, 1], batch_size=None, strict_reference=True):
+                                class_list=[0, 1], batch_size=None, strict_reference=True, cleanup=False, holesize=128):
     """src/fuse_utils.py:36-100 -> numpy int64 (T', H, W). ``strict_reference=False`` corrects the
-    two reference quirks (see the module docstring): T' == T always, and T == 32 yields masks."""
+    two reference quirks (see the module docstring): T' == T always, and T == 32 yields masks.
+    ``cleanup=True``: every returned frame is cleaned on the device (fuse_votes' ``cleanup``, ``holesize``)."""
     fused = segment_a_video_with_fusion_device(video, model, interpolate_last, step, num_clips, fuse_method, class_list,
-                                               batch_size, strict_reference)
+                                               batch_size, strict_reference, cleanup, holesize)
     return fused.to(torch.int64).cpu().numpy()

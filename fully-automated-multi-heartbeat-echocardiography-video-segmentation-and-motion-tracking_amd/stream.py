@@ -35,16 +35,18 @@ class VideoStream:
     (so ``with torch.cuda.stream(s): vs.run(...)`` works), and that stream is ordered after all of it
     when ``run`` returns device masks; with ``inflight`` > 1 every other video runs on a private
     compute stream. Uploads use a private copy stream and a ring of two pinned staging buffers that
-    is reused across videos and calls."""
+    is reused across videos and calls. ``cleanup=True`` cleans every fused frame in the fusion call, on the
+    video's lane stream (fuse_utils.fuse_votes' ``cleanup``, ``holesize``): the curves of ``run(curves=True)``
+    then describe the cleaned masks."""
 
     RING = 2
 
     def __init__(self, model, num_clips=5, step=1, fuse_method="simple", height=112, width=112,
-                 batch_size=None, interpolate_last=True, strict_reference=True, inflight=2):
+                 batch_size=None, interpolate_last=True, strict_reference=True, inflight=2, cleanup=False, holesize=128):
         self.model = model
         self.device = FU._device_of(model)
         self.kw = dict(interpolate_last=interpolate_last, step=step, num_clips=num_clips, fuse_method=fuse_method,
-                       batch_size=batch_size, strict_reference=strict_reference)
+                       batch_size=batch_size, strict_reference=strict_reference, cleanup=cleanup, holesize=holesize)
         self.height, self.width = height, width
         self.copy_stream = torch.cuda.Stream(self.device)
         self.lanes = [torch.cuda.Stream(self.device) for _ in range(max(1, inflight) - 1)]  # private compute streams
@@ -157,7 +159,7 @@ class VideoStream:
 
 
 def segment_videos(frame_videos, model, num_clips=5, step=1, fuse_method="simple", height=112, width=112,
-                   batch_size=None, strict_reference=True, curves=False):
+                   batch_size=None, strict_reference=True, curves=False, cleanup=False, holesize=128):
     """Convenience wrapper: VideoStream(...).run(frame_videos, curves=curves)."""
-    return VideoStream(model, num_clips, step, fuse_method, height, width, batch_size,
-                       strict_reference=strict_reference).run(frame_videos, curves=curves)
+    return VideoStream(model, num_clips, step, fuse_method, height, width, batch_size, strict_reference=strict_reference,
+                       cleanup=cleanup, holesize=holesize).run(frame_videos, curves=curves)

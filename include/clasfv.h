@@ -54,6 +54,17 @@ enum { CLASFV_FUSE_MAJORITY = 0, CLASFV_FUSE_SIMPLE = 1, CLASFV_FUSE_STAPLE = 2,
 /* OR-ed into a clasfv_fuse_votes method: run SIMPLE on its generic kernel instead of the packed
  * 16-vote one (A/B testing; results are identical). */
 #define CLASFV_FUSE_FORCE_GENERIC 0x100
+/* OR-ed into a clasfv_fuse_votes method: clean every fused frame in place after the fusion (the rule is
+ * stated at clasfv_fuse_votes). CLASFV_FUSE_CLEAN_HOLES(n), n in 1..32767, sets the hole threshold in bits
+ * 16..30; without it (n = 0) the threshold is the reference's default, CLASFV_CLEAN_DEFAULT_HOLES. */
+#define CLASFV_FUSE_CLEAN 0x200
+#define CLASFV_FUSE_CLEAN_HOLES(n) ((n) << 16)
+#define CLASFV_CLEAN_DEFAULT_HOLES 128
+/* Largest frame CLASFV_FUSE_CLEAN takes, in pixels. The cleanup kernel keeps one frame in the 160 KiB of a
+ * CU's LDS as a 16-bit label and a flag byte per pixel, 3 B, beside 256 B of state: 52 * 1024 pixels, the
+ * packed SIMPLE kernel's limit (224 x 224 = 50176 fits). A label is a pixel index, so 32-bit labels would halve
+ * the limit and lose 224 x 224. */
+#define CLASFV_CLEAN_MAX_PIXELS 53248
 enum { CLASFV_DTYPE_FP32 = 0, CLASFV_DTYPE_BF16 = 1 };
 /* One more kernel-variant bit (CLASFV_NO_DMA_X3_WIDE in the environment; see the enum below):
  * conv_dma_x3's 128-voxel x 80- / 96-channel blocks on the fp32 engines' 240- and 480-channel convs,
@@ -335,7 +346,35 @@ int clasfv_logit_margin(const float* logits_dev, int n, int H, int W, float* mar
  * STAPLE and ITK voting are restated from their published definitions: LabelFusion itself is absent,
  * so their parity is unpinned). CLASFV_EINVAL for H < 1 or W < 1 and, for MAJORITY / ITKVOTING, T' > 65535.
  * SIMPLE keeps one frame's state in LDS: H * W <= 162816 (160 KB less 1 KB; e.g. 403 x 403), else
- * CLASFV_EBADSHAPE; the packed kernel (K <= 16) serves H * W <= 53248, the generic one everything else. */
+ * CLASFV_EBADSHAPE; the packed kernel (K <= 16) serves H * W <= 53248, the generic one everything else.
+ *
+ * method | CLASFV_FUSE_CLEAN [| CLASFV_FUSE_CLEAN_HOLES(holesize)]: after the fusion kernel, one more launch
+ * on the same stream cleans every fused frame in place (one workgroup per frame, the frame in LDS; no
+ * workspace): cleanupBinary of the reference (src/utils/camus_validate.py:284-352) for label 1 -- keep the
+ * connected component of largest filled area, fill its holes below holesize. With K = 1 and
+ * CLASFV_FUSE_MAJORITY the call cleans an existing 0/1 mask video. A new flag only: the ABI revision is
+ * unchanged, and every method without the flag launches exactly what it launched before. The rule, per
+ * fused frame (this statement is the definition; scikit-image is the reference's implementation of it):
+ *   1. Members are the pixels equal to 1. Components of members are 8-connected (skimage.measure.label's
+ *      default in 2-D). A frame without members is left as it is.
+ *   2. The filled area of a component R is H * W less the pixels outside R that an 8-connected path of
+ *      pixels outside R joins to the outside of the frame, the frame taken as padded with one ring of
+ *      non-members (regionprops' filled_area: binary_fill_holes with a 3 x 3 structure of ones on the
+ *      region's own image). Other components lying in R's holes count towards R.
+ *   3. The component of greatest filled area is kept; among equals, the one whose first pixel in row-major
+ *      order comes first. (The reference leaves a tie to the order numpy.argsort happens to give, so parity
+ *      at a tie is undefined; this rule is defined.)
+ *   4. Of the pixels outside the kept component, every 4-connected component of fewer than holesize pixels
+ *      joins it, whether or not it touches the frame edge (remove_small_holes(connectivity=1), which is
+ *      remove_small_objects on the complement and does not look at the border: a corner pocket cut off by
+ *      the kept component is filled). holesize = 1 fills nothing.
+ *   5. A pixel becomes 1 if kept or filled; otherwise 0 where it was 1; otherwise it keeps its value (ITK
+ *      voting's undecided 2 passes through unless filled over).
+ * The result is idempotent, and a frame's bytes do not depend on T', on the frame's place in the call or on
+ * thread order. scikit-image is not available to this project, so the rule's parity is unpinned, like
+ * SIMPLE's and STAPLE's. CLASFV_EINVAL, before any HIP call, for hole-threshold bits without
+ * CLASFV_FUSE_CLEAN, bit 31 or any other unknown bit; CLASFV_EBADSHAPE, before any launch (so nothing is
+ * fused either), for H * W > CLASFV_CLEAN_MAX_PIXELS with the flag. */
 int clasfv_fuse_votes(const uint8_t* labels_dev, int K, int T, int step, int H, int W, int method,
                       uint8_t* fused_dev, void* stream);
 

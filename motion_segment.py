@@ -8,7 +8,9 @@ announced by a notice -- ``-d cpu`` runs the engine on GPU 0 and returns host ar
 an error. ``-d cuda`` / ``cuda:i`` pick the GPU.
 Extra opt-in flags: ``--synthetic-weights SEED`` with ``--synthetic-recipe echo|random`` (seeded
 weights when no checkpoint is available offline), ``--batch-size`` (clips per forward call) and
-``--no-strict-reference`` (fuse_utils.segment_a_video_with_fusion(strict_reference=False)).
+``--no-strict-reference`` (fuse_utils.segment_a_video_with_fusion(strict_reference=False)); ``--cleanup`` with
+``--holesize N`` cleans every fused frame on the device (the reference's cleanupBinary: largest LV component kept,
+holes below N pixels filled), and the EF, pickles, volume curve and gif are then made from the cleaned masks.
 ``-c gif`` (and ``all``) writes ``<name>_annotated.gif``, the reference's annotated video (LV overlay, title,
 volume curve), rendered on the device (clasfv_amd.render) and encoded by PIL; without PIL the frames are
 written as ``<name>_annotated.npy``. ``-c volume_curve`` (not part of ``all``) pickles the per-frame curve.
@@ -54,7 +56,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-strict-reference", action="store_true",
                     help="correct the reference's plumbing quirks: a single 32-frame clip yields masks instead of "
                          "IndexError, and frames 1..step-1 are kept for step > 1")
-    return ap.parse_args(argv)
+    ap.add_argument("--cleanup", action="store_true",
+                    help="keep the LV component of largest filled area in every fused frame and fill its small holes")
+    ap.add_argument("--holesize", type=int, default=128, metavar="N",
+                    help="with --cleanup: holes of fewer than N pixels are filled (1..32767)")
+    args = ap.parse_args(argv)
+    if not 1 <= args.holesize <= 32767:
+        ap.error(f"--holesize {args.holesize}: an integer in 1..32767 expected")
+    return args
 
 
 def read_video(path):
@@ -117,7 +126,8 @@ def main(argv=None):
     fused = segment_a_video_with_fusion_device(video, model=model, interpolate_last=True, step=args.step,
                                                num_clips=args.fuse, fuse_method=args.fuse_method, class_list=[0, 1],
                                                batch_size=args.batch_size,
-                                               strict_reference=not args.no_strict_reference)
+                                               strict_reference=not args.no_strict_reference, cleanup=args.cleanup,
+                                               holesize=args.holesize)
     segmentations = fused.to(torch.int64).cpu().numpy()  # what segment_a_video_with_fusion returns
     predicted_efs, edes_pairs = compute_ef_using_putative_clips(segmentations, test_pat_index=args.path,
                                                                 return_edes=True)
