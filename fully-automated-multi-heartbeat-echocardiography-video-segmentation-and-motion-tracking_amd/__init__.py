@@ -11,6 +11,7 @@ libclasfv.so). Modules:
   warp        motion-field warp (generate_2dmotion_field + grid_sample semantics); track /
               track_labels / apply_sequence_deformation: a frame through a chain of fields
   echo        EF from masks (compute_ef_using_putative_clips, get2dPucks, EDESpairs)
+  beats       every detected heartbeat tracked through the motion fields: tracked masks, Dice, EF
   preprocess  zeroone_normalizer on the device
   dist        clip-wise sharding over ranks + all-gather of per-clip logits
 """

@@ -172,17 +172,21 @@ def divide_to_consecutive_clips(video, clip_length=CLIP, interpolate_last=False)
     return build_clips(v, table, interpolate_last)
 
 
-def run_model(model, clips, batch_size=None):
-    """Segmentation logits (n,2,32,H,W) of every clip; the motion output is discarded as in the
-    reference (src/fuse_utils.py:59)."""
+def run_model(model, clips, batch_size=None, return_motion=False):
+    """Segmentation logits (n,2,32,H,W) of every clip. By default the motion output is discarded as in the
+    reference (src/fuse_utils.py:59); ``return_motion=True`` returns ``(logits, motion)`` with the motion
+    fields (n,4,32,H,W) float32 of the same forwards (beats.track_beats tracks through them)."""
     n = clips.shape[0]
     if batch_size is None:
         batch_size = DEFAULT_BATCH if hasattr(model, "engine") else 1
-    outs = []
+    outs, mots = [], []
     for s in range(0, n, batch_size):
-        seg, _ = model(clips[s:s + batch_size])
+        seg, mot = model(clips[s:s + batch_size])
         outs.append(seg.to(clips.device, torch.float32))
-    return torch.cat(outs) if len(outs) > 1 else outs[0].contiguous()
+        if return_motion:
+            mots.append(mot.to(clips.device, torch.float32))
+    join = lambda xs: torch.cat(xs) if len(xs) > 1 else xs[0].contiguous()
+    return (join(outs), join(mots)) if return_motion else join(outs)
 
 
 def check_fuse_votes_args(shape, step):

@@ -14,6 +14,10 @@ holes below N pixels filled), and the EF, pickles, volume curve and gif are then
 ``-c gif`` (and ``all``) writes ``<name>_annotated.gif``, the reference's annotated video (LV overlay, title,
 volume curve), rendered on the device (clasfv_amd.render) and encoded by PIL; without PIL the frames are
 written as ``<name>_annotated.npy``. ``-c volume_curve`` (not part of ``all``) pickles the per-frame curve.
+``-c tracking`` (not part of ``all``) tracks every detected heartbeat through the model's motion fields
+(clasfv_amd.beats.track_beats) and writes ``<name>_beat_tracking.pkl``: per beat the tracked masks, their Dice
+against the segmentation, their volume curves and the EF that tracking alone gives; ``-c tracking_gif`` (not part
+of ``all``) writes ``<name>_tracking.gif``, the annotated video with the tracked masks as the difference image.
 Video input: any file OpenCV can decode if cv2 is installed (as the reference), or ``.npy`` holding
 (T,H,W,3) uint8 RGB frames.
 """
@@ -43,7 +47,9 @@ def parse_args(argv=None):
     ap.add_argument("-c", "--content", required=False, type=str,
                     help="Content of the output: gif (the annotated video <name>_annotated.gif: overlay, title and "
                          "volume curve; <name>_annotated.npy when PIL is missing), binary, binary_video, all; also "
-                         "volume_curve (not part of all): the per-frame LV area, length, radii and volume",
+                         "volume_curve (not part of all): the per-frame LV area, length, radii and volume; tracking "
+                         "(not part of all): every heartbeat tracked through the motion fields, <name>_beat_tracking.pkl; "
+                         "tracking_gif (not part of all): <name>_tracking.gif, segmentation against tracked masks",
                     default="binary")
     ap.add_argument("--height", required=False, type=int, help="Height of image (pretrain model uses 112)", default=112)
     ap.add_argument("--width", required=False, type=int, help="Width of image (pretrain model uses 112)", default=112)
@@ -168,6 +174,37 @@ def main(argv=None):
     if "volume_curve" in content:  # from the device masks, in one kernel launch (echo.lv_curve)
         with open(os.path.join(args.output, filename + "_lv_volume_curve.pkl"), "wb") as f:
             pickle.dump(lv_curve(fused).asdict(), f)
+    if "tracking" in content or "tracking_gif" in content:
+        # every detected beat through the motion fields, on the device (beats.track_beats); the pairs are the
+        # ones reported above
+        from clasfv_amd import beats
+        tracking = beats.track_beats(video, fused, model, pairs=[(int(d), int(s)) for d, s in edes_pairs],
+                                     batch_size=args.batch_size)
+        if "tracking" in content:
+            result = tracking.asdict()
+            if args.verbose:
+                why = dict(result["skipped"])
+                for i, (ed, es) in enumerate(result["pairs"]):
+                    if i in why:
+                        print("Beat #{:d}: ED {:d} & ES {:d} not tracked: {}".format(i + 1, ed, es, why[i]))
+                        continue
+                    print("Beat #{:d}: ED {:d} & ES {:d} EF segmented {:.2f}, tracked forward {:.2f}, tracked backward "
+                          "{:.2f}, mean forward Dice {:.4f}".format(
+                              i + 1, ed, es, result["ef_seg"][i], result["ef_forward"][i], result["ef_backward"][i],
+                              float(np.mean(result["dice_forward"][i]))))
+            with open(os.path.join(args.output, filename + "_beat_tracking.pkl"), "wb") as f:
+                pickle.dump(result, f)
+        if "tracking_gif" in content:
+            from clasfv_amd import render
+            frames = render.annotate_video(video[:, :fused.shape[0]], fused, truth=tracking.tracked_video()).cpu().numpy()
+            try:
+                render.write_gif(frames, os.path.join(args.output, filename + "_tracking.gif"))
+            except RuntimeError as e:
+                if "PIL" not in str(e):
+                    raise
+                print("notice: PIL (Pillow) is not installed: the tracking frames are written as "
+                      f"{filename}_tracking.npy ((T,H,W,3) uint8 RGB) instead of a GIF", file=sys.stderr)
+                np.save(os.path.join(args.output, filename + "_tracking.npy"), frames)
     return segmentations, predicted_efs, edes_pairs
 
 
